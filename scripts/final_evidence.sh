@@ -6,5 +6,5 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 bash scripts/pmc_bulk.sh pmc_final_ctr128 "--mode ctr --bits 128" &&
 bash scripts/pmc_bulk.sh pmc_final_ctr256 "--mode ctr --bits 256" &&
-timeout -k 10 300 python bench.py --steps 1000 --warmup 3 --no-aes256 --no-scatter --no-stream --no-other-impl \
+timeout -k 10 300 python bench.py --full --steps 1000 --warmup 3 --no-aes256 --no-scatter --no-stream --no-other-impl \
     > gpurun_out/sustained_1000.json 2> gpurun_out/sustained_1000.err && cat gpurun_out/sustained_1000.json

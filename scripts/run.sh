@@ -4,10 +4,10 @@
 #   gpurun --timeout 900 -- bash scripts/run.sh <suite> [args...]
 #
 # suites
-#   validate            pytest -m gpu, smoke(), default bench.py   (round-end checks)
+#   validate            pytest -m gpu, smoke(), bench.py --full   (round-end checks)
 #   test [pytest args]  pytest -m gpu (optionally a subset: test tests/test_gpu_engine.py -k cbc)
 #   bench [bench args]  bench.py with the given flags
-#   rehearse N [args]   bench.py --gpus N --gib 2 self-spawned, N ranks sharing the box's GPU (gloo)
+#   rehearse N [args]   bench.py --full --gpus N --gib 2 self-spawned, N ranks sharing the box's GPU (gloo)
 #   kt NAME -- CMD...   rocprofv3 kernel trace + stats of CMD, summarised to gpurun_out/NAME/kernels.txt
 #   pmc NAME "COUNTERS" -- CMD...   one counter pass (<= 8 SQ, 4 TCC, ...) of CMD, CSV in gpurun_out/NAME
 #   otbench [otbench args]          bin/otbench JSON lines
@@ -38,7 +38,7 @@ validate)
     tail -1 $D/pytest_gpu.log
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1 || { cat $D/smoke.log; exit 1; }
     tail -1 $D/smoke.log
-    timeout -k 10 600 python bench.py > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+    timeout -k 10 600 python bench.py --full > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
     cat $D/bench.json
     ;;
 test)
@@ -56,7 +56,7 @@ rehearse)
     n=${1:-2}
     shift || true
     # N shards must fit ONE GPU: 2 GiB each unless the args say otherwise (argparse keeps the last --gib)
-    OTC_DIST_BACKEND=gloo OTC_SHARE_GPUS=1 timeout -k 10 600 python bench.py --gpus "$n" --no-clock --gib 2 "$@" \
+    OTC_DIST_BACKEND=gloo OTC_SHARE_GPUS=1 timeout -k 10 600 python bench.py --full --gpus "$n" --no-clock --gib 2 "$@" \
         > $OUT/rehearse_dp$n.txt 2>&1 || { tail -30 $OUT/rehearse_dp$n.txt; exit 1; }
     grep '^{' $OUT/rehearse_dp$n.txt | tail -1 > $OUT/rehearse_dp$n.json
     cat $OUT/rehearse_dp$n.json

@@ -26,7 +26,7 @@ done; done
 bash scripts/power_probe.sh "bitslice" > $O/power.txt 2>&1 || { tail -5 $O/power.txt; exit 1; }
 cp -r gpurun_out/power $O/ 2>/dev/null
 mkdir -p $O/kt
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt/db -o run -- python3 bench.py --steps 5 --warmup 1 --no-scatter --no-stream > $O/kt/run.log 2>&1 || { tail -20 $O/kt/run.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt/db -o run -- python3 bench.py --full --steps 5 --warmup 1 --no-scatter --no-stream > $O/kt/run.log 2>&1 || { tail -20 $O/kt/run.log; exit 1; }
 db=$(find $O/kt/db -name '*.db' | head -1)
 python3 tools/rocpd_summary.py "$db" > $O/kt/kernels.txt && head -12 $O/kt/kernels.txt
 python3 - "$O" <<'PY'

@@ -3,7 +3,9 @@ reads (metric/value/unit/n_gpus/steps/warmup/ms_per_step/...), the metric and
 config BASELINE.json names, and value consistent with ms_per_step.
 
 The GPU test runs the real headline step on a small shard (0.25 GiB instead of
-64 GiB, so it finishes in seconds); the CPU test only checks the CLI surface."""
+64 GiB, so it finishes in seconds); the CPU test only checks the CLI surface.
+The extras are read from ``--full`` runs; a plain run carries the headline
+alone and, with ``--dump-outputs``, writes the last step's output."""
 import json
 import os
 import subprocess
@@ -20,7 +22,7 @@ def test_bench_cli_help():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in r.stdout
 
 
@@ -44,7 +46,7 @@ def _cpu_bench(*extra, timeout=300):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gib", "0.0005",
-                           "--steps", "2", "--warmup", "1", "--scatter-rounds", "2", *extra],
+                           "--steps", "2", "--warmup", "1", "--scatter-rounds", "2", "--full", *extra],
                           capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
 
 
@@ -117,7 +119,7 @@ def test_bench_json_line(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--gib", "0.25", "--no-clock",
+                        "--gib", "0.25", "--no-clock", "--full",
                         "--scatter-mib", "64", "--scatter-rounds", "2", "--stream-gib", "0.25",
                         "--stream-passes", "2"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
@@ -167,6 +169,126 @@ def test_bench_json_line(gpu):
     assert d["refmethod_verified"] is True
     assert d["refmethod_ecb256_1000mib_gbps"] > 2.41
     assert d["kernel_only_ecb256_1000mib_gbps"] > d["pinned_e2e_ecb256_1000mib_gbps"] > 0
+
+
+FULL_ONLY = ("rccl_ranks", "stream_ctr_verified", "refmethod_verified", "aes256_ctr_verified",
+             "bitsliced_ctr_verified", "ttable_ctr_verified", "aes256_ecb_verified", "energy_window_s")
+
+
+def _bench_inputs(n):
+    """key, counter and (on the host) plaintext as bench.py draws them"""
+    import torch
+
+    gen = torch.Generator().manual_seed(1337)
+    key = bytes(torch.randint(0, 256, (16,), generator=gen, dtype=torch.uint8).tolist())
+    torch.randint(0, 256, (32,), generator=gen, dtype=torch.uint8)  # the AES-256 key
+    counter = bytes(torch.randint(0, 256, (16,), generator=gen, dtype=torch.uint8).tolist())
+    plain = torch.randint(0, 256, (n,), generator=torch.Generator().manual_seed(1000), dtype=torch.uint8)
+    return key, counter, plain.numpy().tobytes()
+
+
+def _plain_cpu_bench(gib, out):
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gib", gib,
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_lean_and_dumps_whole_small_shard(tmp_path):
+    """Without --full: the headline keys and nothing that takes a run of its
+    own; --dump-outputs writes the whole of a small shard as float32, equal to
+    the oracle's CTR of the seeded input (3 in-place steps = one encryption)."""
+    import numpy as np
+
+    from our_tree_amd.models import cpu_ref
+
+    d = _plain_cpu_bench("0.0005", tmp_path)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    n = d["config"]["per_gpu_bytes"]
+    # value is rounded to 3 decimals, and small on the host
+    assert d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3) / 1e9, abs=1e-3)
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["verified_sample"] is None and d["per_rank"][0]["verified"] is None
+    assert os.listdir(tmp_path) == ["ctr_out_rank0.npy"]
+    a = np.load(tmp_path / "ctr_out_rank0.npy")
+    assert a.dtype == np.float32 and a.shape == (n,)
+    key, counter, plain = _bench_inputs(n)
+    assert a.astype(np.uint8).tobytes() == cpu_ref.ctr(key, counter, plain)
+
+
+def test_dump_outputs_sample_is_reproducible(tmp_path):
+    """A shard above the dump budget: head, seeded 4 KiB chunks, tail -- 12 MiB
+    as float32 (48 MB <= 64 MB), identical from run to run, head and tail equal
+    to the oracle's."""
+    import numpy as np
+
+    from our_tree_amd.models import cpu_ref
+
+    d = _plain_cpu_bench("0.02", tmp_path / "a")
+    _plain_cpu_bench("0.02", tmp_path / "b")
+    a = np.load(tmp_path / "a" / "ctr_out_rank0.npy")
+    b = np.load(tmp_path / "b" / "ctr_out_rank0.npy")
+    assert a.dtype == np.float32 and a.shape == (12 << 20,) and a.nbytes <= 64e6
+    assert np.array_equal(a, b)
+    n = d["config"]["per_gpu_bytes"]
+    assert n > a.size
+    key, counter, plain = _bench_inputs(n)
+    S = 1 << 16
+    assert a[:S].astype(np.uint8).tobytes() == cpu_ref.ctr(key, counter, plain[:S])
+    assert a[-S:].astype(np.uint8).tobytes() == cpu_ref.ctr(key, counter, plain[n - S:], (n - S) // 16)
+    # every sampled 4 KiB chunk is a chunk of the oracle's output
+    want = np.frombuffer(cpu_ref.ctr(key, counter, plain), dtype=np.uint8)
+    rows = {want[i:i + 4096].tobytes() for i in range(0, n - 4095, 4096)}
+    edge = (12 << 20) // 8
+    mid = a[edge:-edge].astype(np.uint8).reshape(-1, 4096)
+    assert all(r.tobytes() in rows for r in mid)
+
+
+@pytest.mark.gpu
+def test_plain_bench_dump_on_gpu(gpu, tmp_path):
+    """The plain run on the GPU: lean line, and the dumped sample's head and
+    tail are the oracle's CTR of the shard fill_random_ made (3 in-place steps)."""
+    import numpy as np
+    import torch
+
+    from our_tree_amd import ops
+    from our_tree_amd.models import cpu_ref
+
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--gib", "0.25", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    d = json.loads(lines[0])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["metric"] == "GB/s AES-128-CTR (whole node)" and d["unit"] == "GB/s" and d["dtype"] == "uint8"
+    assert d["steps"] == 2 and d["higher_is_better"] is True
+    n = d["config"]["per_gpu_bytes"]
+    assert n == int(0.25 * (1 << 30))
+    assert d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3) / 1e9, rel=0.01)
+    assert d["value"] > 100.0  # the HIP kernel ran
+    assert not [k for k in FULL_ONLY if k in d]
+    a = np.load(tmp_path / "ctr_out_rank0.npy")
+    assert a.dtype == np.float32 and a.shape == (12 << 20,)
+    key, counter, _ = _bench_inputs(16)
+    plain = ops.fill_random_(torch.empty(n, dtype=torch.uint8, device=gpu), seed=1000)
+    S = 1 << 16
+    head, tail = plain[:S].cpu().numpy().tobytes(), plain[n - S:].cpu().numpy().tobytes()
+    assert a[:S].astype(np.uint8).tobytes() == cpu_ref.ctr(key, counter, head)
+    assert a[-S:].astype(np.uint8).tobytes() == cpu_ref.ctr(key, counter, tail, (n - S) // 16)
 
 
 @pytest.mark.parametrize("script", ["bench.py", "benchmarks/cbc_scatter.py", "benchmarks/stream_ctr.py",
