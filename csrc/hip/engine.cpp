@@ -150,6 +150,13 @@ bool alloc_fault()
 
 extern "C" void otc_fault_inject_alloc(long after) { otc_dev::g_fault_alloc.store(after < 0 ? -1 : after); }
 
+extern "C" long otc_fault_inject_pending(void)
+{
+    /* the countdown itself: alloc_fault leaves it at -1 when it fires */
+    const long v = otc_dev::g_fault_alloc.load(std::memory_order_relaxed);
+    return v < 0 ? -1 : v;
+}
+
 using namespace otc_rt;
 
 namespace {
@@ -357,10 +364,15 @@ thread_local uint64_t g_split_word = 0, g_split_nunits = 0, g_split_ttwaves = 0,
  * counter / no auxiliary stream).  bs_only: impl "bitslice" -- the T-table
  * kernel's back counter starts full, so the bitsliced kernel (bs_wgs
  * workgroups) takes every unit and one T-table workgroup runs the rest.
+ * front(n): the grid T-table kernel on st over units [0, n) and nothing
+ * else -- what the T-table claim kernel, already queued, leaves out when the
+ * bitsliced half does not launch (no_front where there is no such half).
  * *ran: the kernels actually used. */
-template <class TT, class BS, class PLAIN>
+inline hipError_t no_front(uint64_t) { return hipErrorInvalidValue; }
+
+template <class TT, class BS, class PLAIN, class FRONT>
 hipError_t split_claim(uint64_t nunits, uint64_t min_units, bool bs_only, unsigned bs_wgs, hipStream_t st, int *ran,
-                       TT tt, BS bs, PLAIN plain)
+                       TT tt, BS bs, PLAIN plain, FRONT front)
 {
     *ran = OTC_IMPL_TTABLE;
     g_split_fallback = "";
@@ -429,11 +441,14 @@ hipError_t split_claim(uint64_t nunits, uint64_t min_units, bool bs_only, unsign
          * process's first split call run the T-table half alone (front 0,
          * profiles/r6/coresidency/matrix.jsonl; with the warm-up the first
          * call co-runs, matrix_warm_aux.jsonl).
-         * The bitsliced half failing (no memory for its key table) leaves the
-         * T-table claim kernel to take every unit -- unless it was told to
-         * take none (bs_only): then the T-table alone redoes the call.  The
-         * join is recorded either way (a failure after its launch must still
-         * be waited for). */
+         * The bitsliced half failing (no memory for its key table, its only
+         * step before its launches) leaves the T-table claim kernel to take
+         * what it can claim: units [pf, nunits) and the blocks past the last
+         * unit -- none of the units under bs_only.  Units [0, pf) (bs_only:
+         * every unit) were the bitsliced waves' and are still owed: front()
+         * runs exactly those on st after the join, so no block is enciphered
+         * twice when the call is in place.  The join is recorded either way
+         * (a failure after its launch must still be waited for). */
         const hipError_t eb = bs_wgs ? bs(cl, a.s) : hipSuccess;
         if (eb != hipSuccess) {
             (void)hipGetLastError();
@@ -444,7 +459,7 @@ hipError_t split_claim(uint64_t nunits, uint64_t min_units, bool bs_only, unsign
             e = hipStreamWaitEvent(st, a.join_t, 0);
         if (e == hipSuccess) {
             if (eb == hipSuccess && bs_wgs) *ran = bs_only ? OTC_IMPL_BITSLICE : OTC_IMPL_SPLIT;
-            else if (bs_only) e = plain();
+            else if (const uint64_t owed = bs_only ? nunits : (uint64_t)pf; eb != hipSuccess && owed) e = front(owed);
             if (e == hipSuccess && g_split_stats.load(std::memory_order_relaxed)) {
                 /* the counter's last value sits where the agent-scope atomics
                  * left it: read it with one (an ordinary copy can see a stale
@@ -539,12 +554,14 @@ hipError_t ecb_split(const void *in, void *out, uint64_t nblocks, const otc_aes_
             nunits, 2, form == FORM_BS, bs_wgs_for(form), st, ran,
             [&](SplitClaim cl, hipStream_t ts) { return otc_impl::tt_ecb_encrypt_claim(in, out, nblocks, K, cl, ts); },
             [&](SplitClaim cl, hipStream_t s) { return otc_impl::bs_claim(BS_ECB, in, out, nblocks, K, nullptr, cl, s); },
-            [&]() { return otc_impl::tt_ecb_encrypt(in, out, nblocks, K, st); });
+            [&]() { return otc_impl::tt_ecb_encrypt(in, out, nblocks, K, st); },
+            [&](uint64_t n) { return otc_impl::tt_ecb_encrypt(in, out, n * otc_dev::CLAIM_UNIT, K, st); });
     return split_claim(
         nunits, 2, form == FORM_BS, bs_wgs_for(form), st, ran,
         [&](SplitClaim cl, hipStream_t ts) { return otc_impl::tt_ecb_decrypt_claim(in, out, nblocks, K, cl, ts); },
         [&](SplitClaim cl, hipStream_t s) { return otc_impl::bs_claim(BS_ECB_DEC, in, out, nblocks, K, nullptr, cl, s); },
-        [&]() { return otc_impl::tt_ecb_decrypt(in, out, nblocks, K, st); });
+        [&]() { return otc_impl::tt_ecb_decrypt(in, out, nblocks, K, st); },
+        [&](uint64_t n) { return otc_impl::tt_ecb_decrypt(in, out, n * otc_dev::CLAIM_UNIT, K, st); });
 }
 
 hipError_t cbc_dec_split(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, const uint8_t iv[16],
@@ -557,7 +574,9 @@ hipError_t cbc_dec_split(const void *in, void *out, uint64_t nblocks, const otc_
         nblocks / otc_dev::CLAIM_UNIT, 2, form == FORM_BS, bs_wgs_for(form), st, ran,
         [&](SplitClaim cl, hipStream_t ts) { return otc_impl::tt_cbc_decrypt_claim(in, out, nblocks, K, ivc, cl, ts); },
         [&](SplitClaim cl, hipStream_t s) { return otc_impl::bs_claim(BS_CBC_DEC, in, out, nblocks, K, ivw, cl, s); },
-        [&]() { return otc_impl::tt_cbc_decrypt(in, out, nblocks, K, ivc, st); });
+        [&]() { return otc_impl::tt_cbc_decrypt(in, out, nblocks, K, ivc, st); },
+        /* a prefix of the chain is the same call, shorter */
+        [&](uint64_t n) { return otc_impl::tt_cbc_decrypt(in, out, n * otc_dev::CLAIM_UNIT, K, ivc, st); });
 }
 
 hipError_t cfb_dec_split(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, const uint32_t ivw[4],
@@ -567,7 +586,8 @@ hipError_t cfb_dec_split(const void *in, void *out, uint64_t nblocks, const otc_
         nblocks / otc_dev::CLAIM_UNIT, 2, form == FORM_BS, bs_wgs_for(form), st, ran,
         [&](SplitClaim cl, hipStream_t ts) { return otc_impl::tt_cfb_decrypt_claim(in, out, nblocks, K, ivw, cl, ts); },
         [&](SplitClaim cl, hipStream_t s) { return otc_impl::bs_claim(BS_CFB_DEC, in, out, nblocks, K, ivw, cl, s); },
-        [&]() { return otc_impl::tt_cfb_decrypt(in, out, nblocks, K, ivw, st); });
+        [&]() { return otc_impl::tt_cfb_decrypt(in, out, nblocks, K, ivw, st); },
+        [&](uint64_t n) { return otc_impl::tt_cfb_decrypt(in, out, n * otc_dev::CLAIM_UNIT, K, ivw, st); });
 }
 
 /* Segment decryption (CBC / CFB128 over independent segments of 2^shift
@@ -605,7 +625,15 @@ hipError_t seg_dec_split(bool cfb, const void *in, void *out, size_t seg_blocks,
         [&](SplitClaim cl, hipStream_t s) {
             return otc_impl::bs_claim_seg(cfb ? BS_CFB_DEC_SEG : BS_CBC_DEC_SEG, in, out, nblocks, K, iv0, sh, cl, s);
         },
-        plain);
+        plain,
+        /* whole segments: one longer than a unit is finished past unit n - 1,
+         * rewriting what the claim kernel wrote there with the same bytes
+         * (the decryptions read only the input, never in place) */
+        [&](uint64_t n) {
+            const uint64_t ns = (n * otc_dev::CLAIM_UNIT + seg_blocks - 1) / seg_blocks;
+            return cfb ? otc_impl::tt_cfb_decrypt_seg(in, out, seg_blocks, ns, K, iv0, st)
+                       : otc_impl::tt_cbc_decrypt_seg(in, out, seg_blocks, ns, K, iv0, st);
+        });
 }
 
 /* the kernel family the calling thread's last AES call ran (otc_last_impl) */
@@ -653,7 +681,7 @@ hipError_t seg_enc_run(bool cfb, const void *in, void *out, size_t seg_bytes, si
         nseg / SEG_UNIT, 16, false, 0u, st, &g_last_impl,
         [&](SplitClaim cl, hipStream_t ts) { return otc_impl::tt_seg_encrypt_claim(cfb, in, out, seg_blocks, nseg, K, iv0, cl, ts); },
         [&](SplitClaim, hipStream_t) { return hipErrorInvalidValue; /* no VALU half: bs_wgs = 0 never calls it */ },
-        grid);
+        grid, no_front);
 }
 
 
@@ -812,7 +840,7 @@ static int ctr_common(const void *in, void *out, size_t nbytes, const otc_aes_ke
             otc_impl::tt_ctr_claim_units(nbytes, c.lo), 2, false, 0u, st, &g_last_impl,
             [&](SplitClaim cl, hipStream_t ts) { return otc_impl::tt_ctr_claim(in, out, nbytes, *k, c, wrap64, cl, ts); },
             [&](SplitClaim, hipStream_t) { return hipErrorInvalidValue; /* bs_wgs 0: no VALU half */ },
-            [&]() { return otc_impl::tt_ctr(in, out, nbytes, *k, c, wrap64, st); });
+            [&]() { return otc_impl::tt_ctr(in, out, nbytes, *k, c, wrap64, st); }, no_front);
     } else {
         e = otc_impl::tt_ctr(in, out, nbytes, *k, c, wrap64, st);
     }
@@ -957,7 +985,7 @@ extern "C" int otc_aes_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *key
                                  return otc_impl::tt_ctr_batch(msgs, keys, tile_msg, tile_first, ntiles, tile_blocks, nr,
                                                                ts, &cl);
                              },
-                             [&](SplitClaim, hipStream_t) { return hipErrorInvalidValue; /* no VALU half */ }, plain)
+                             [&](SplitClaim, hipStream_t) { return hipErrorInvalidValue; /* no VALU half */ }, plain, no_front)
                        : plain();
     if (e != hipSuccess) return hip_fail(e, "ctr_batch launch");
     return OTC_OK;

@@ -85,8 +85,8 @@ int otc_pick_impl(int impl, int bits, int mode, uint64_t nbytes);
  * OTC_IMPL_BITSLICE or OTC_IMPL_SPLIT (OTC_IMPL_AUTO before any call).  Set
  * by otc_aes_ctr / _rfc3686 / _ctr_stream, otc_aes_ecb, the CBC / CFB128
  * decryptions and every segment call; a split or bitsliced request that fell
- * back to the T-table (too few units, no memory for the claim counter) reports
- * OTC_IMPL_TTABLE. */
+ * back to the T-table (too few units, no memory for the claim counter, the
+ * bitsliced half failing to launch) reports OTC_IMPL_TTABLE. */
 int otc_last_impl(void);
 /* Split accounting, a profiling mode (off by default): with
  * otc_split_stats(1) every split call on this thread waits for its kernels
@@ -415,6 +415,10 @@ void otc_release_resources(void);
  * (device buffers, NUMA-pinned host windows, per-call kernel tables), so the
  * error paths can be exercised on a healthy GPU; after < 0 disarms. */
 void otc_fault_inject_alloc(long after);
+/* The hook's countdown: >= 0 while armed (that many allocations still pass
+ * before the one that fails), -1 once the failure has fired or when disarmed.
+ * A test reads it after the call under test to know its fault landed. */
+long otc_fault_inject_pending(void);
 
 /* Device-resident multi-GPU CTR: buffers dev_bufs[g] (already on GPU g) hold
  * shard g of `shard_bytes`; all GPUs encrypt in place concurrently with the

@@ -217,6 +217,7 @@ def _declare_gpu(lib):
         "otc_multi_release": (None, []),
         "otc_release_resources": (None, []),
         "otc_fault_inject_alloc": (None, [ctypes.c_long]),
+        "otc_fault_inject_pending": (ctypes.c_long, []),
         "otc_device_numa_node": (c_int, [c_int]),
         "otc_engine_numa_node": (c_int, [c_vp]),
         "otc_engine_staging": (c_vp, [c_vp, c_int]),

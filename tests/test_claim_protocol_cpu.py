@@ -92,3 +92,31 @@ def test_preassigned_first_units(seed):
             seen += us
         assert sorted(seen) == list(range(nunits)), (nunits, nb, nf)
         assert sorted(front) == list(range(len(front)))
+
+
+@pytest.mark.parametrize("seed", [31, 32])
+def test_front_never_launched_leaves_prefix_to_host(seed):
+    """The bitsliced half fails to launch after the T-table claim kernel was
+    queued with pf > 0 (engine.cpp split_claim): no front wave ever runs, and
+    the back side -- pre-assigned units and claims, in any order -- hands out
+    exactly [pf, nunits).  Units [0, pf) are owed by the host; its rerun of
+    that prefix and nothing else covers every unit exactly once."""
+    rnd = random.Random(seed)
+    owed = 0
+    for _ in range(300):
+        nunits = rnd.randint(2, 300)
+        nb, nf = rnd.randint(1, 24), rnd.randint(1, 12)
+        pb = min(nunits, nb)
+        pf = min(nunits - pb, nf)
+        back = [nunits - 1 - w for w in range(pb)]
+        counter, live = 0, nb
+        while live:
+            counter, us = claim_pre(counter, nunits, True, pf, pb)
+            if not us:
+                live -= 1  # a wave whose claim failed exits its loop
+            back += us
+        assert sorted(back) == list(range(pf, nunits)), (nunits, nb, nf)
+        host = list(range(pf))  # split_claim's front(pf) on the caller's stream
+        assert sorted(back + host) == list(range(nunits)), (nunits, nb, nf)
+        owed += pf > 0
+    assert owed > 100  # the case under test, not only pf == 0
