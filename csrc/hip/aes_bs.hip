@@ -49,10 +49,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "otc_bitslice.h"
 #include "otc_device.h"
+#include "otc_kernels.h"
 
 using namespace otc_dev;
 using namespace otc_bs;
@@ -92,7 +94,7 @@ template <int MODE> constexpr bool is_seg = MODE == BS_CBC_DEC_SEG || MODE == BS
  * runs the first and the last task (wave 0 / wave 1) if they are partial. */
 enum : uint32_t { BS_FULL_ONLY = 1, BS_EDGE_ONLY = 2 };
 
-/* the modes BS_CTR .. BS_CFB_DEC: otc_device.h (engine.cpp names them too) */
+/* the modes BS_CTR .. BS_CFB_DEC: otc_device.h */
 
 __device__ __forceinline__ W lane_mask(uint32_t lane, int n) { return (W)(0u - ((lane >> n) & 1u)); }
 
@@ -700,8 +702,6 @@ namespace otc_impl {
 
 OTC_STRACE_READER(strace_read_bs)
 
-hipError_t tt_ctr(const void *, void *, size_t, const otc_aes_key &, Ctr128, bool, hipStream_t);
-
 hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
                   hipStream_t st)
 {
@@ -728,7 +728,7 @@ hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K
     return launch<BS_CTR>(P, K, st);
 }
 
-/* One-time warm-up of the split's bitsliced half (engine.cpp aux_take, when
+/* One-time warm-up of the split's bitsliced half (split.cpp aux_take, when
  * a device's first auxiliary stream is created): the runtime loads this
  * file's code object at the first lookup of one of its kernels, and a first
  * split call otherwise paid for that after its T-table half had started --
@@ -739,43 +739,33 @@ hipError_t bs_preload()
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_aes_bs_claim<14, BS_ECB>));
 }
 
-/* The bitsliced halves of a claimed split: the whole buffer (block 0's
- * predecessor is iv_le), units from the front of `cl` */
-hipError_t bs_claim(int mode, const void *in, void *out, uint64_t nblocks, const otc_aes_key &K,
-                    const uint32_t iv_le[4], SplitClaim cl, hipStream_t st)
+/* The bitsliced half of a claimed split: the whole buffer, units from the
+ * front of `cl`.  Block 0's predecessor is the IV (LE words of its bytes);
+ * over segments of 2^seg_shift blocks, segment s chains from IV_s = iv + s. */
+hipError_t bs_claim(const Job &j, SplitClaim cl, hipStream_t st)
 {
+    const otc_aes_key &K = *j.key;
     BsParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nblocks = nblocks;
-    for (int i = 0; i < 4; ++i) P.iv[i] = iv_le ? iv_le[i] : 0u;
+    P.in = (const uint8_t *)j.in;
+    P.out = (uint8_t *)j.out;
+    P.nblocks = j.nblocks;
     P.cl = cl;
-    switch (mode) {
-    case BS_ECB: return launch<BS_ECB>(P, K, st);
-    case BS_ECB_DEC: return launch<BS_ECB_DEC>(P, K, st);
-    case BS_CBC_DEC: return launch<BS_CBC_DEC>(P, K, st);
-    case BS_CFB_DEC: return launch<BS_CFB_DEC>(P, K, st);
-    default: return hipErrorInvalidValue;
+    if (job_is_seg(j)) {
+        if (seg_shift_of(j.seg_blocks) < 0) return hipErrorInvalidValue;
+        P.iv0 = ctr_from_bytes(j.iv);
+        P.seg_shift = (uint32_t)seg_shift_of(j.seg_blocks);
+    } else if (j.iv) {
+        memcpy(P.iv, j.iv, 16);
     }
-}
-
-/* ... and of a claimed split over independent segments of 2^seg_shift
- * blocks, segment s chained from IV_s = iv0 + s */
-hipError_t bs_claim_seg(int mode, const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, Ctr128 iv0,
-                        uint32_t seg_shift, SplitClaim cl, hipStream_t st)
-{
-    BsParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nblocks = nblocks;
-    P.iv0 = iv0;
-    P.seg_shift = seg_shift;
-    P.cl = cl;
-    switch (mode) {
-    case BS_CBC_DEC_SEG: return launch<BS_CBC_DEC_SEG>(P, K, st);
-    case BS_CFB_DEC_SEG: return launch<BS_CFB_DEC_SEG>(P, K, st);
-    default: return hipErrorInvalidValue;
+    switch (j.mode) {
+    case JOB_ECB_ENC: return launch<BS_ECB>(P, K, st);
+    case JOB_ECB_DEC: return launch<BS_ECB_DEC>(P, K, st);
+    case JOB_CBC_DEC: return launch<BS_CBC_DEC>(P, K, st);
+    case JOB_CFB_DEC: return launch<BS_CFB_DEC>(P, K, st);
+    case JOB_CBC_DEC_SEG: return launch<BS_CBC_DEC_SEG>(P, K, st);
+    case JOB_CFB_DEC_SEG: return launch<BS_CFB_DEC_SEG>(P, K, st);
     }
+    return hipErrorInvalidValue;
 }
 
 } // namespace otc_impl

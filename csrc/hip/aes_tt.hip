@@ -37,8 +37,10 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "otc_device.h"
+#include "otc_kernels.h"
 
 using namespace otc_dev;
 
@@ -863,7 +865,6 @@ __global__ __launch_bounds__(THREADS) void k_aes_cbc_enc_seg_g(CbcSegParams P, o
  * seg_enc_run): a claim unit is 64 segments, one per lane of a wave, taken
  * from the back; workgroup 0 first runs the segments past the last full unit.
  * It runs alone (engine.cpp seg_enc_run): no VALU half claims from the front. */
-constexpr uint32_t SEG_UNIT = 64;
 template <int NR, int G, bool CFB>
 __global__ __launch_bounds__(1024) OTC_CLAIM_ATTR void k_aes_seg_enc_tt_claim(CbcSegParams P, otc_aes_key K)
 {
@@ -1012,7 +1013,6 @@ struct BatchParams {
     uint64_t ntiles;
     SplitClaim cl; /* ctr != nullptr: BATCH_UNIT-tile units, first handed out, the rest claimed */
 };
-constexpr uint64_t BATCH_UNIT = 8; /* tiles per claimed unit (8 x 4 KiB at B = 4) */
 
 __device__ __forceinline__ uint32_t ufl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -1376,7 +1376,7 @@ hipError_t launch_ctr_batch_nr(const BatchParams &P, int tile_blocks, hipStream_
 
 } // namespace
 
-/* ---- internal entry points used by engine.cpp ---------------------------- */
+/* ---- host entry points (otc_kernels.h) ------------------------------------- */
 namespace otc_impl {
 
 OTC_STRACE_READER(strace_read_tt)
@@ -1397,13 +1397,75 @@ hipError_t tt_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const 
     }
 }
 
-hipError_t tt_ecb_encrypt(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, hipStream_t st)
+/* a job's parameter blocks: the encryption-direction kernels' (ECB
+ * encryption, CFB decryption) and the decryption-direction kernels' */
+static EncParams enc_params(const Job &j, uint64_t nblocks, const SplitClaim *cl = nullptr)
 {
     EncParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
+    P.in = (const uint8_t *)j.in;
+    P.out = (uint8_t *)j.out;
     P.nfull = nblocks;
-    return launch_enc<E_ECB>(P, K, st);
+    if (j.mode == JOB_CFB_DEC) memcpy(P.iv, j.iv, 16); /* LE words of the IV bytes, as the kernels load blocks */
+    if (j.mode == JOB_CFB_DEC_SEG) {
+        const int sh = seg_shift_of(j.seg_blocks);
+        P.ctr = ctr_from_bytes(j.iv);
+        P.seg_blocks = j.seg_blocks;
+        P.seg_shift = sh < 0 ? 64u : (uint32_t)sh;
+    }
+    if (cl) P.cl = *cl;
+    return P;
+}
+
+static DecParams dec_params(const Job &j, uint64_t nblocks, const SplitClaim *cl = nullptr)
+{
+    DecParams P{};
+    P.in = (const uint8_t *)j.in;
+    P.out = (uint8_t *)j.out;
+    P.nfull = nblocks;
+    if (j.mode != JOB_ECB_DEC) P.iv = ctr_from_bytes(j.iv);
+    if (j.mode == JOB_CBC_DEC_SEG) P.seg_shift = (uint32_t)std::max(seg_shift_of(j.seg_blocks), 0);
+    if (cl) P.cl = *cl;
+    return P;
+}
+
+hipError_t tt_run(const Job &j, uint64_t nblocks, hipStream_t st)
+{
+    const otc_aes_key &K = *j.key;
+    /* whole segments: of a prefix (the split's owed units), one that ends
+     * inside a segment is finished past it */
+    if (job_is_seg(j)) nblocks = (nblocks + j.seg_blocks - 1) / j.seg_blocks * j.seg_blocks;
+    switch (j.mode) {
+    case JOB_ECB_ENC: return launch_enc<E_ECB>(enc_params(j, nblocks), K, st);
+    case JOB_CFB_DEC: return launch_enc<E_CFB_DEC>(enc_params(j, nblocks), K, st);
+    case JOB_CFB_DEC_SEG: return launch_enc<E_CFB_DEC_SEG>(enc_params(j, nblocks), K, st);
+    case JOB_ECB_DEC: return launch_dec<D_ECB>(dec_params(j, nblocks), K, st);
+    case JOB_CBC_DEC: return launch_dec<D_CBC>(dec_params(j, nblocks), K, st);
+    case JOB_CBC_DEC_SEG: {
+        if (seg_shift_of(j.seg_blocks) >= 0) return launch_dec<D_CBC_SEG>(dec_params(j, nblocks), K, st); /* in-kernel IVs */
+        /* any other length: one chain, then each segment's first block redone with its IV */
+        const uint64_t nseg = nblocks / j.seg_blocks;
+        const hipError_t e = launch_dec<D_CBC>(dec_params(j, nblocks), K, st);
+        if (e != hipSuccess || nseg < 2) return e;
+        hipLaunchKernelGGL(k_cbc_seg_fixup, dim3((unsigned)((nseg - 1 + 255) / 256)), dim3(256), 0, st,
+                           (const uint8_t *)j.in, (uint8_t *)j.out, j.seg_blocks, nseg, ctr_from_bytes(j.iv));
+        return hipGetLastError();
+    }
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t tt_claim(const Job &j, SplitClaim cl, hipStream_t st)
+{
+    const otc_aes_key &K = *j.key;
+    switch (j.mode) {
+    case JOB_ECB_ENC: return launch_enc_claim<E_ECB>(enc_params(j, j.nblocks, &cl), K, st);
+    case JOB_CFB_DEC: return launch_enc_claim<E_CFB_DEC>(enc_params(j, j.nblocks, &cl), K, st);
+    case JOB_CFB_DEC_SEG: return launch_enc_claim<E_CFB_DEC_SEG>(enc_params(j, j.nblocks, &cl), K, st);
+    case JOB_ECB_DEC: return launch_dec_claim<D_ECB>(dec_params(j, j.nblocks, &cl), K, st);
+    case JOB_CBC_DEC: return launch_dec_claim<D_CBC>(dec_params(j, j.nblocks, &cl), K, st);
+    case JOB_CBC_DEC_SEG: return launch_dec_claim<D_CBC_SEG>(dec_params(j, j.nblocks, &cl), K, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 /* one 1024- or 256-thread workgroup per CU (the 128 KiB 4-table image) */
@@ -1428,8 +1490,8 @@ hipError_t launch_ctr_cached(CtrParams P, const otc_aes_key &K, uint64_t ctr_lo,
     }
 }
 
-hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
-                  hipStream_t st)
+/* all of CtrParams but the launch shape's part (shift, cbase.lo) */
+static CtrParams ctr_params(const void *in, void *out, size_t nbytes, Ctr128 c, bool wrap64)
 {
     CtrParams P{};
     P.in = (const uint8_t *)in;
@@ -1438,6 +1500,13 @@ hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K
     P.tail = (uint32_t)(nbytes % 16);
     P.wrap64 = wrap64 ? 1u : 0u;
     P.cbase.hi = c.hi;
+    return P;
+}
+
+hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
+                  hipStream_t st)
+{
+    const CtrParams P = ctr_params(in, out, nbytes, c, wrap64);
     switch (K.nr) {
     case 10: return launch_ctr_cached<10>(P, K, c.lo, st);
     case 12: return launch_ctr_cached<12>(P, K, c.lo, st);
@@ -1447,23 +1516,18 @@ hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K
 }
 
 /* the persistent claim form of tt_ctr: its virtual range (the blocks plus
- * ctr0 mod 4096 in front) in 2048-block units */
+ * ctr0 mod the bulk shape's step in front) in 2048-block units */
+constexpr uint64_t CTR_BULK_PER = 1024ull * OTC_TT_CTR_B; /* as the grid kernel's bulk shape */
 uint64_t tt_ctr_claim_units(size_t nbytes, uint64_t ctr_lo)
 {
-    return (nbytes / 16 + (nbytes % 16 ? 1 : 0) + (ctr_lo & 4095u) + CLAIM_UNIT - 1) / CLAIM_UNIT;
+    return (nbytes / 16 + (nbytes % 16 ? 1 : 0) + (ctr_lo & (CTR_BULK_PER - 1)) + CLAIM_UNIT - 1) / CLAIM_UNIT;
 }
 
 hipError_t tt_ctr_claim(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
                         SplitClaim cl, hipStream_t st)
 {
-    CtrParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nbytes / 16;
-    P.tail = (uint32_t)(nbytes % 16);
-    P.wrap64 = wrap64 ? 1u : 0u;
-    P.cbase.hi = c.hi;
-    P.shift = c.lo & 4095u; /* as the grid kernel's bulk shape (PER = 1024 x 4) */
+    CtrParams P = ctr_params(in, out, nbytes, c, wrap64);
+    P.shift = c.lo & (CTR_BULK_PER - 1);
     P.cbase.lo = c.lo - P.shift;
     P.cl = cl;
     const dim3 g(cl.wgs ? cl.wgs : (unsigned)num_cus()), b(1024);
@@ -1473,136 +1537,6 @@ hipError_t tt_ctr_claim(const void *in, void *out, size_t nbytes, const otc_aes_
     case 14: hipLaunchKernelGGL(k_aes_ctr_tt_persist<14>, g, b, 0, st, P, K); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-hipError_t tt_cfb_decrypt(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K,
-                          const uint32_t iv_le[4], hipStream_t st)
-{
-    EncParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    for (int i = 0; i < 4; ++i) P.iv[i] = iv_le[i];
-    return launch_enc<E_CFB_DEC>(P, K, st);
-}
-
-hipError_t tt_ecb_decrypt(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, hipStream_t st)
-{
-    DecParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    return launch_dec<D_ECB>(P, K, st);
-}
-
-hipError_t tt_cbc_decrypt(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, Ctr128 iv,
-                          hipStream_t st)
-{
-    DecParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    P.iv = iv;
-    return launch_dec<D_CBC>(P, K, st);
-}
-
-/* The T-table halves of a claimed co-resident split (engine.cpp): the whole
- * buffer, units from the back of `cl`, plus the blocks past its last unit. */
-hipError_t tt_ecb_encrypt_claim(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, SplitClaim cl,
-                                hipStream_t st)
-{
-    EncParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    P.cl = cl;
-    return launch_enc_claim<E_ECB>(P, K, st);
-}
-
-hipError_t tt_cfb_decrypt_claim(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K,
-                                const uint32_t iv_le[4], SplitClaim cl, hipStream_t st)
-{
-    EncParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    for (int i = 0; i < 4; ++i) P.iv[i] = iv_le[i];
-    P.cl = cl;
-    return launch_enc_claim<E_CFB_DEC>(P, K, st);
-}
-
-hipError_t tt_ecb_decrypt_claim(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, SplitClaim cl,
-                                hipStream_t st)
-{
-    DecParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    P.cl = cl;
-    return launch_dec_claim<D_ECB>(P, K, st);
-}
-
-hipError_t tt_cbc_decrypt_claim(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, Ctr128 iv,
-                                SplitClaim cl, hipStream_t st)
-{
-    DecParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    P.iv = iv;
-    P.cl = cl;
-    return launch_dec_claim<D_CBC>(P, K, st);
-}
-
-/* the T-table halves of a claimed split over power-of-two segments
- * (2^seg_shift blocks, IV_s = iv0 + s) */
-hipError_t tt_cbc_decrypt_seg_claim(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, Ctr128 iv0,
-                                    uint32_t seg_shift, SplitClaim cl, hipStream_t st)
-{
-    DecParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    P.iv = iv0;
-    P.seg_shift = seg_shift;
-    P.cl = cl;
-    return launch_dec_claim<D_CBC_SEG>(P, K, st);
-}
-
-hipError_t tt_cfb_decrypt_seg_claim(const void *in, void *out, uint64_t nblocks, const otc_aes_key &K, Ctr128 iv0,
-                                    uint32_t seg_shift, SplitClaim cl, hipStream_t st)
-{
-    EncParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = nblocks;
-    P.ctr = iv0;
-    P.seg_blocks = 1ull << seg_shift;
-    P.seg_shift = seg_shift;
-    P.cl = cl;
-    return launch_enc_claim<E_CFB_DEC_SEG>(P, K, st);
-}
-
-hipError_t tt_cbc_decrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                              const otc_aes_key &K, Ctr128 iv0, hipStream_t st)
-{
-    DecParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = seg_blocks * nseg;
-    P.iv = iv0;
-    if (seg_blocks && (seg_blocks & (seg_blocks - 1)) == 0) { /* power of two: in-kernel IVs */
-        uint32_t sh = 0;
-        while ((1ull << sh) < seg_blocks) ++sh;
-        P.seg_shift = sh;
-        return launch_dec<D_CBC_SEG>(P, K, st);
-    }
-    hipError_t e = launch_dec<D_CBC>(P, K, st);
-    if (e != hipSuccess || nseg < 2) return e;
-    const uint64_t nfix = nseg - 1;
-    hipLaunchKernelGGL(k_cbc_seg_fixup, dim3((unsigned)((nfix + 255) / 256)), dim3(256), 0, st,
-                       (const uint8_t *)in, (uint8_t *)out, seg_blocks, nseg, iv0);
     return hipGetLastError();
 }
 
@@ -1695,24 +1629,6 @@ hipError_t tt_seg_encrypt_claim(bool cfb, const void *in, void *out, uint64_t se
     case 14: return go(std::integral_constant<int, 14>{});
     default: return hipErrorInvalidValue;
     }
-}
-
-hipError_t tt_cfb_decrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                              const otc_aes_key &K, Ctr128 iv0, hipStream_t st)
-{
-    EncParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.nfull = seg_blocks * nseg;
-    P.ctr = iv0;
-    P.seg_blocks = seg_blocks;
-    P.seg_shift = 64;
-    if ((seg_blocks & (seg_blocks - 1)) == 0) {
-        uint32_t sh = 0;
-        while ((1ull << sh) < seg_blocks) ++sh;
-        P.seg_shift = sh;
-    }
-    return launch_enc<E_CFB_DEC_SEG>(P, K, st);
 }
 
 } // namespace otc_impl

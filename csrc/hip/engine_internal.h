@@ -1,7 +1,8 @@
 /*
  * engine_internal.h -- helpers shared by the host runtime translation units
- * (engine.cpp: device ops / keys / info; pipeline.cpp: host streaming engine
- * and multi-GPU jobs).  Not part of the public C API (otc.h).
+ * (engine.cpp: device ops / keys / info; split.cpp: kernel choice and the
+ * claimed runs; pipeline.cpp: host streaming engine and multi-GPU jobs).
+ * Not part of the public C API (otc.h).
  */
 #ifndef OTC_ENGINE_INTERNAL_H
 #define OTC_ENGINE_INTERNAL_H
@@ -10,10 +11,12 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "otc.h"
 #include "otc_device.h"
+#include "otc_kernels.h"
 
 namespace otc_rt {
 
@@ -24,10 +27,42 @@ int set_err(int code, const std::string &msg);
 std::string last_err();
 int hip_fail(hipError_t e, const char *what);
 
-Ctr128 ctr_from_bytes(const uint8_t c[16]);
+using otc_dev::ctr_from_bytes;
 Ctr128 ctr_add(Ctr128 c, uint64_t n, bool wrap64);
 int check_key(const otc_aes_key *k, int dir);
-/* destroy the pooled auxiliary streams of the ECB split (engine.cpp) */
+
+/* ---- split.cpp: which kernels a call runs, and the claimed runs ---------- */
+int check_impl(int impl);
+/* CTR's choice (no split); ECB's and the decryptions' are made by job_run */
+int pick_impl(int impl, int bits, size_t ctr_bytes);
+/* from these sizes the T-table runs as a persistent claim kernel */
+size_t tt_ctr_persistent_min();
+bool segenc_persistent(size_t nbytes, size_t nseg);
+
+/* pick (impl, OTC_IMPL, size) and run one ECB / decryption call: the grid
+ * T-table kernel, the persistent T-table kernel alone, the co-resident split
+ * or the bitsliced claim kernel alone.  *ran: the kernels actually used. */
+hipError_t job_run(const otc_impl::Job &job, int impl, hipStream_t st, int *ran);
+
+/* a non-owning reference to a callable, for the span of one call (no
+ * allocation, unlike std::function): launch(cl) enqueues the claim kernel,
+ * launch(nullptr) the grid kernel */
+struct LaunchRef {
+    void *obj;
+    hipError_t (*call)(void *, const otc_dev::SplitClaim *);
+    template <class F>
+    LaunchRef(F &&f)
+        : obj((void *)&f),
+          call([](void *o, const otc_dev::SplitClaim *cl) { return (*(std::remove_reference_t<F> *)o)(cl); })
+    {
+    }
+    hipError_t operator()(const otc_dev::SplitClaim *cl) const { return call(obj, cl); }
+};
+/* A persistent T-table claim kernel by itself on the caller's stream: nunits
+ * claim units, the first ones handed out; the grid kernel when there are
+ * fewer than min_units or no memory for the counter. */
+hipError_t claim_alone(uint64_t nunits, uint64_t min_units, hipStream_t st, LaunchRef launch);
+/* destroy the pooled auxiliary streams of the split */
 void aux_release_all();
 
 /* roctx range for rocprofv3 --marker-trace (a no-op unless a tool is

@@ -89,6 +89,13 @@ __device__ __forceinline__ uint32_t rotl24(uint32_t x) { return __builtin_amdgcn
 struct Ctr128 {
     uint64_t hi, lo;
 };
+inline Ctr128 ctr_from_bytes(const uint8_t c[16]) /* host */
+{
+    Ctr128 v{0, 0};
+    for (int i = 0; i < 8; ++i) v.hi = (v.hi << 8) | c[i];
+    for (int i = 8; i < 16; ++i) v.lo = (v.lo << 8) | c[i];
+    return v;
+}
 
 /* counter + idx; `wrap64` keeps the carry out of the high half (RFC 3686 /
  * AES-NI layout of the reference, aesni.c:139-143). */
@@ -114,7 +121,7 @@ enum : int { BS_CTR = 0, BS_ECB = 1, BS_ECB_DEC = 2, BS_CBC_DEC = 3, BS_CFB_DEC 
                * instead of block i-1 */
               BS_CBC_DEC_SEG = 5, BS_CFB_DEC_SEG = 6 };
 
-/* Work claiming of a co-resident split (engine.cpp split_claim): the T-table
+/* Work claiming of a co-resident split (split.cpp split_run): the T-table
  * and the bitsliced kernel take units of ONE buffer from a shared 64-bit
  * counter -- the bitsliced kernel from the front (count in the low 32 bits),
  * the T-table kernel from the back (high 32 bits) -- so both run until the
@@ -134,7 +141,9 @@ enum : int { BS_CTR = 0, BS_ECB = 1, BS_ECB_DEC = 2, BS_CBC_DEC = 3, BS_CFB_DEC 
  * covers the units between.  Otherwise every wave's FIRST claim lands on the
  * word at once -- 4096 T-table waves queue ~45 us on one address (~90 atomics
  * per us), the last of them idle that long (docs/PERF.md round 6). */
-constexpr uint32_t CLAIM_UNIT = 2048u;
+constexpr uint32_t CLAIM_UNIT = 2048u; /* blocks */
+constexpr uint32_t SEG_UNIT = 64;       /* segments: the persistent segment-encryption kernel */
+constexpr uint64_t BATCH_UNIT = 8;      /* tiles: the claimed batch kernel (8 x 4 KiB at B = 4) */
 struct SplitClaim {
     unsigned long long *ctr; /* zeroed (stream-ordered) before the launches */
     uint32_t nunits;         /* full units */

@@ -1,0 +1,90 @@
+/*
+ * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
+ * aes_bs.hip, stream_ops.hip), declared once: included by their callers
+ * (engine.cpp, split.cpp) and by the files that define them, so every
+ * definition is checked against the declaration its callers see.  Not part
+ * of the public C API (otc.h).
+ */
+#ifndef OTC_KERNELS_H
+#define OTC_KERNELS_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "otc.h"
+#include "otc_device.h"
+
+namespace otc_impl {
+
+using otc_dev::Ctr128;
+using otc_dev::SplitClaim;
+
+/* One call of ECB or of a parallel decryption, as every kernel family takes
+ * it: the grid T-table kernel, the T-table claim kernel and the bitsliced
+ * claim kernel each fill their parameter block from this in one place. */
+enum JobMode : int { JOB_ECB_ENC, JOB_ECB_DEC, JOB_CBC_DEC, JOB_CFB_DEC, JOB_CBC_DEC_SEG, JOB_CFB_DEC_SEG };
+struct Job {
+    JobMode mode;
+    const void *in;
+    void *out;
+    uint64_t nblocks;
+    const otc_aes_key *key;
+    const uint8_t *iv;   /* 16 bytes (segment modes: IV of segment 0, IV_s = iv + s); null for ECB */
+    uint64_t seg_blocks; /* segment modes: blocks per segment (>= 1) */
+};
+inline bool job_is_seg(const Job &j) { return j.mode == JOB_CBC_DEC_SEG || j.mode == JOB_CFB_DEC_SEG; }
+/* log2 of a power-of-two segment length, else -1 (such segments run on the
+ * grid T-table kernel only) */
+inline int seg_shift_of(uint64_t seg_blocks)
+{
+    return seg_blocks && !(seg_blocks & (seg_blocks - 1)) ? __builtin_ctzll(seg_blocks) : -1;
+}
+
+/* ---- aes_tt.hip ---------------------------------------------------------- */
+/* the grid T-table kernel over the first nblocks blocks of the job (segment
+ * modes: rounded up to whole segments) */
+hipError_t tt_run(const Job &j, uint64_t nblocks, hipStream_t st);
+/* the T-table claim kernel: the whole buffer, units from the back of `cl`,
+ * plus the blocks past its last unit (power-of-two segments only) */
+hipError_t tt_claim(const Job &j, SplitClaim cl, hipStream_t st);
+hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
+                  hipStream_t st);
+uint64_t tt_ctr_claim_units(size_t nbytes, uint64_t ctr_lo);
+hipError_t tt_ctr_claim(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
+                        SplitClaim cl, hipStream_t st);
+hipError_t tt_ctr_shift(const void *body_in, void *body_out, size_t len, const otc_aes_key &K, Ctr128 c,
+                        hipStream_t st);
+hipError_t xor_small(const void *in, void *out, uint32_t n, const uint8_t *ks, hipStream_t st);
+hipError_t tt_cbc_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg, const otc_aes_key &K,
+                              Ctr128 iv0, hipStream_t st);
+hipError_t tt_cfb_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg, const otc_aes_key &K,
+                              Ctr128 iv0, hipStream_t st);
+hipError_t tt_seg_encrypt_claim(bool cfb, const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
+                                const otc_aes_key &K, Ctr128 iv0, SplitClaim cl, hipStream_t st);
+/* cl null: the static split over the waves; else claimed runs of BATCH_UNIT tiles */
+hipError_t tt_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const uint32_t *tile_msg,
+                        const uint64_t *tile_first, uint64_t ntiles, int tile_blocks, int nr, hipStream_t st,
+                        const SplitClaim *cl);
+uint64_t tt_ctr_batch_units(uint64_t ntiles);
+int strace_read_tt(unsigned long long *buf, int max);
+
+/* ---- aes_bs.hip ---------------------------------------------------------- */
+hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
+                  hipStream_t st);
+/* the bitsliced claim kernel: the whole buffer, units from the front of `cl` */
+hipError_t bs_claim(const Job &j, SplitClaim cl, hipStream_t st);
+hipError_t bs_preload();
+int strace_read_bs(unsigned long long *buf, int max);
+
+/* ---- stream_ops.hip ------------------------------------------------------ */
+hipError_t k_xor(const void *a, const void *b, void *out, size_t n, hipStream_t st);
+hipError_t k_fill_random(void *p, size_t n, uint64_t seed, hipStream_t st);
+hipError_t k_checksum(const void *p, size_t n, uint64_t *out, hipStream_t st);
+hipError_t k_clock(uint64_t *out, uint64_t delay_ticks, uint64_t ticks, hipStream_t st);
+hipError_t k_rc4_multi(const uint8_t *keys, int keylen, size_t nstreams, size_t len, size_t drop, const void *in,
+                       void *out, hipStream_t st);
+hipError_t k_rc4_states(void *states, size_t nstreams, size_t len, const void *in, void *out, hipStream_t st);
+
+} // namespace otc_impl
+
+#endif

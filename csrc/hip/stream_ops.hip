@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "otc_device.h"
+#include "otc_kernels.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>

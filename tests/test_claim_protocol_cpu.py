@@ -68,7 +68,7 @@ def claim_pre(counter, nunits, back, pf, pb):
 
 @pytest.mark.parametrize("seed", [21, 22])
 def test_preassigned_first_units(seed):
-    """engine.cpp split_claim hands the T-table waves (w < pb) unit
+    """split.cpp split_run hands the T-table waves (w < pb) unit
     nunits - 1 - w and the bitsliced waves (j < pf) unit j before any claim
     (otc_device.h first_unit): with any interleaving every unit is still
     taken exactly once, the front holds a prefix."""
@@ -97,7 +97,7 @@ def test_preassigned_first_units(seed):
 @pytest.mark.parametrize("seed", [31, 32])
 def test_front_never_launched_leaves_prefix_to_host(seed):
     """The bitsliced half fails to launch after the T-table claim kernel was
-    queued with pf > 0 (engine.cpp split_claim): no front wave ever runs, and
+    queued with pf > 0 (split.cpp split_run): no front wave ever runs, and
     the back side -- pre-assigned units and claims, in any order -- hands out
     exactly [pf, nunits).  Units [0, pf) are owed by the host; its rerun of
     that prefix and nothing else covers every unit exactly once."""
@@ -116,7 +116,7 @@ def test_front_never_launched_leaves_prefix_to_host(seed):
                 live -= 1  # a wave whose claim failed exits its loop
             back += us
         assert sorted(back) == list(range(pf, nunits)), (nunits, nb, nf)
-        host = list(range(pf))  # split_claim's front(pf) on the caller's stream
+        host = list(range(pf))  # split_run: tt_run over the owed units on the caller's stream
         assert sorted(back + host) == list(range(nunits)), (nunits, nb, nf)
         owed += pf > 0
     assert owed > 100  # the case under test, not only pf == 0

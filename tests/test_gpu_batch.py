@@ -72,6 +72,42 @@ def test_packed_batch_matches_oracle(gpu):
         assert got[o:o + n] == cpu_ref.ctr(keys[kidx[::-1][j]], ctrs[::-1][j].tobytes(), src[o:o + n])
 
 
+def test_claimed_batch_matches_oracle(gpu):
+    """A launch of >= 65536 tiles runs claimed tile runs (otc_aes_ctr_batch ->
+    claim_alone), not the static split over the waves.  One launch is made per
+    key size, so the AES-256 messages alone carry just over 65536 1 KiB tiles
+    (43 messages of ~1.5 MiB, odd lengths, one counter at the 2^64 carry); the
+    AES-128 launch beside it (tiny and empty messages) stays static.  Out of
+    place, then in place."""
+    rng = np.random.default_rng(21)
+    big = [int(v) | 1 for v in rng.integers(3 << 19, (3 << 19) + (1 << 16), 43)]
+    lens = big + [0, 1, 15, 16, 17, 1023, 1025, 0, 4097, 100001]
+    slots = [(n + 15) // 16 * 16 for n in lens]
+    buf = _messages(gpu, [sum(slots)], 22)[0]
+    keys = [os.urandom(32), os.urandom(16)]
+    kidx = [0] * len(big) + [1, 0, 1, 1, 0, 1, 1, 1, 0, 1]
+    ctrs = rng.integers(0, 256, (len(lens), 16), dtype=np.uint8)
+    ctrs[2, 8:] = np.frombuffer((2**64 - 1000).to_bytes(8, "big"), dtype=np.uint8)  # carry inside a big message
+    src = host(buf)
+    b = ops.CtrBatch.packed(buf, lens, keys, ctrs, key_index=kidx, tile_blocks=64)
+    tiles = {nr: t for *_, t, nr in b._launches}
+    assert tiles[14] >= 65536 > tiles[10] > 0, tiles
+    b.run()
+    torch.cuda.synchronize()
+    offs = np.cumsum([0] + slots[:-1])
+    refs = [cpu_ref.ctr(keys[kidx[i]], ctrs[i].tobytes(), src[o:o + n]) for i, (o, n) in enumerate(zip(offs, lens))]
+    got = host(b.out)
+    for i, (o, n) in enumerate(zip(offs, lens)):
+        assert got[o:o + n] == refs[i], f"message {i} ({n} bytes)"
+    b2 = ops.CtrBatch.packed(buf, lens, keys, ctrs, out=buf, key_index=kidx, tile_blocks=64)
+    assert {nr: t for *_, t, nr in b2._launches} == tiles
+    b2.run()
+    torch.cuda.synchronize()
+    got = host(buf)
+    for i, (o, n) in enumerate(zip(offs, lens)):
+        assert got[o:o + n] == refs[i], f"message {i} ({n} bytes), in place"
+
+
 def test_ctr_batch_in_place_replay(gpu):
     """in == out, planned once and run twice: CTR twice is the identity."""
     sizes = [4096 * 3, 1000, 8192 + 48]

@@ -100,7 +100,7 @@ def test_bitslice_ctr_falls_back_without_group_table(inject, gpu, bits):
 
 @pytest.mark.parametrize("k", [0, 1])
 def test_bitslice_ecb_alloc_failure_falls_back(inject, gpu, k):
-    """impl="bitslice" ECB is the bitsliced claim kernel alone (split_claim,
+    """impl="bitslice" ECB is the bitsliced claim kernel alone (split_run,
     bs_only).  If its work counter (allocation 0) or key table (allocation 1)
     cannot be allocated, the T-table runs the call instead -- complete output,
     and last_impl() says so -- and the next call runs bitsliced again."""
@@ -147,7 +147,7 @@ def test_split_under_alloc_faults(inject, gpu, k, want):
 
 
 # ---- every claimed mode with its bitsliced half not launched ----------------
-# engine.cpp split_claim queues the T-table claim kernel first, told that
+# split.cpp split_run queues the T-table claim kernel first, told that
 # units [0, pf) are the bitsliced waves' (impl "bitslice": every unit).  When
 # the bitsliced half's key table (allocation 1; allocation 0 is the claim
 # counter) cannot be allocated those units are still owed, and the host reruns
@@ -225,7 +225,7 @@ def _where(y, t):
 
 
 def _split_front(n, cus):
-    """split_claim's pre-assignment for an impl="split" call of n bytes"""
+    """split_run's pre-assignment for an impl="split" call of n bytes"""
     nunits = n // UNIT
     pb = min(nunits, 16 * cus)
     return nunits, min(nunits - pb, 4 * cus)
@@ -337,9 +337,10 @@ def test_bitslice_alone_key_table_fails(inject, gpu, name, bits):
 
 
 # ---- the persistent T-table forms without their claim counter ---------------
-# ECB and the decryptions from 512 MiB, CTR from 512 MiB and segment encryption
-# from 1 GiB run the T-table as a claim kernel (split_claim with no bitsliced
-# half); allocation 0, the counter, failing sends them to the grid kernel.
+# ECB and the decryptions from 512 MiB, CTR from 512 MiB, segment encryption
+# from 1 GiB and batches from 65536 tiles run the T-table as a claim kernel by
+# itself (split.cpp claim_alone); allocation 0, the counter, failing sends them
+# to the grid kernel.
 
 def _windows(n, size=16384):
     return [(a, min(n, a + size)) for a in (0, (n // 2) & ~(size - 1), (n - size + 15) & ~15)]
@@ -400,3 +401,33 @@ def test_persistent_segment_encrypt_without_claim_counter(inject, gpu, mode):
     for a, b in _windows(n):  # 16 KiB windows on segment boundaries: n and the window are multiples of 512
         assert a % seg == 0
         assert _host(y[a:b]) == oracle(key, cpu_ref.ctr128_add(iv0, a // seg), _host(x[a:b]), seg), (a, b)
+
+
+def test_claimed_batch_without_claim_counter(inject, gpu):
+    """The batch of test_gpu_batch.py::test_claimed_batch_matches_oracle (its
+    AES-256 launch has >= 65536 tiles and runs claimed tile runs; the small
+    AES-128 launch before it consults no allocation): without the counter the
+    static kernel runs, with the same output."""
+    rng = np.random.default_rng(21)
+    big = [int(v) | 1 for v in rng.integers(3 << 19, (3 << 19) + (1 << 16), 43)]
+    lens = big + [0, 1, 15, 16, 17, 1023, 1025, 0, 4097, 100001]
+    buf = torch.empty(sum((n + 15) // 16 * 16 for n in lens), dtype=torch.uint8, device=gpu)
+    ops.fill_random_(buf, seed=22)
+    keys = [_rnd(32, 23).tobytes(), _rnd(16, 24).tobytes()]
+    kidx = [0] * len(big) + [1, 0, 1, 1, 0, 1, 1, 1, 0, 1]
+    ctrs = rng.integers(0, 256, (len(lens), 16), dtype=np.uint8)
+    ctrs[2, 8:] = np.frombuffer((2**64 - 1000).to_bytes(8, "big"), dtype=np.uint8)
+    b = ops.CtrBatch.packed(buf, lens, keys, ctrs, key_index=kidx, tile_blocks=64)
+    tiles = {nr: t for *_, t, nr in b._launches}
+    assert tiles[14] >= 65536 > tiles[10] > 0, tiles
+    b.out.zero_()  # the slots' padding is not written
+    inject(0)
+    b.run()
+    torch.cuda.synchronize()
+    assert _pending() == -1
+    y = b.out.clone()
+    inject(-1)
+    b.out.zero_()
+    b.run()
+    torch.cuda.synchronize()
+    assert torch.equal(y, b.out), _where(y, b.out)

@@ -88,7 +88,7 @@ def test_pipeline_overlaps_beside_busy_streams(gpu, rccl_world1, busy_streams):
     assert ratios[len(ratios) // 2] < 0.75, ratios
 
 
-GIB2 = 2 << 30  # the split's threshold (engine.cpp split_min)
+GIB2 = 2 << 30  # the split's threshold (split.cpp SPLIT_MIN)
 
 SPLIT_CALLS = {
     "ECB-256": lambda ops, x, o, k, iv: ops.ecb_encrypt(x, k, out=o),
@@ -187,7 +187,7 @@ def test_split_captured_in_graph(gpu):
     """A split call captured into a HIP graph (torch.cuda.CUDAGraph: stream
     capture of the fork / join events, the claim counter's stream-ordered
     allocation and both halves' launches) replays to the right bytes; a call
-    made while capturing never synchronises (engine.cpp aux_take: no warm-up
+    made while capturing never synchronises (split.cpp aux_take: no warm-up
     under capture)."""
     from our_tree_amd import ops
 

@@ -1,6 +1,6 @@
 // Co-residency probe for the claimed splits: can a workgroup of kernel B
 // start on a CU while a workgroup of kernel A (persistent, one per CU) runs
-// there?  The splits (csrc/hip/engine.cpp split_claim) assume a T-table
+// there?  The splits (csrc/hip/split.cpp split_run) assume a T-table
 // workgroup (1024 threads, 128 KiB LDS, 4 waves per SIMD) and one bitsliced
 // wave per SIMD share every CU; a claim-counter readback showed the bitsliced
 // side taking no unit when the T-table kernel holds every CU.
