@@ -688,12 +688,7 @@ hipError_t launch_nr(const BsParams &P, const otc_aes_key &K, hipStream_t st)
 template <int MODE>
 hipError_t launch(const BsParams &P, const otc_aes_key &K, hipStream_t st)
 {
-    switch (K.nr) {
-    case 10: return launch_nr<10, MODE>(P, K, st);
-    case 12: return launch_nr<12, MODE>(P, K, st);
-    case 14: return launch_nr<14, MODE>(P, K, st);
-    default: return hipErrorInvalidValue;
-    }
+    return otc_impl::with_rounds(K.nr, [&](auto nr) { return launch_nr<decltype(nr)::value, MODE>(P, K, st); });
 }
 
 } // namespace

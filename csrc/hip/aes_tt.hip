@@ -33,7 +33,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -66,8 +65,6 @@ namespace {
 
 __device__ const AesTables g_tab = make_tables();
 
-
-
 /* second table (byte 2 of the address taken from lane word byte 2 = 1) */
 constexpr uint32_t SEL_HI(int k) { return 0x0c020000u | ((uint32_t)(4 + k) << 8); }
 
@@ -85,18 +82,6 @@ __device__ __forceinline__ uint32_t lds_at(const uint32_t *tbl, uint32_t byte_ad
  * lookups take the integer LDS address instead. */
 struct DynTbl {
 };
-
-/* Negative control for the co-residency test (tests/test_gpu_queues.py):
- * `make variant NAME=padclaim VFLAGS=-DOTC_DIAG_PAD_CLAIM` pads the T-table
- * claim kernels' register descriptors to a 4-waves-per-SIMD budget -- what the
- * round-4 static-LDS build did by accident -- so no bitsliced wave fits beside
- * them and the split's halves run one after the other.  Never in the release
- * build. */
-#ifdef OTC_DIAG_PAD_CLAIM
-#define OTC_CLAIM_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
-#else
-#define OTC_CLAIM_ATTR
-#endif
 __device__ __forceinline__ uint32_t lds_at(DynTbl, uint32_t byte_addr)
 {
     return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)byte_addr;
@@ -126,17 +111,30 @@ __device__ __forceinline__ uint32_t tt_addr(uint32_t w, uint32_t lkk, int k)
  * so again one v_perm per lookup (byte 1 <- x, bytes 0/2 <- a per-lane,
  * per-table constant) and no rotations: 16 perm + 8 bitop3 per round instead
  * of 16 + 12 + 8.  Bank = lane & 31 for every lookup -> conflict free. */
+/* the word that fills 16-byte row q (< 8192) of the image of T0 = t0 */
+template <class Q>
+__device__ __forceinline__ uint32_t tbl4_row(const uint32_t *t0, Q q)
+{
+    const Q r = q >> 12, x = (q >> 4) & 255, half = (q >> 3) & 1;
+    const Q k = 2 * r + half;
+    const uint32_t t = t0[x];
+    return k ? ((t << (8 * k)) | (t >> (32 - 8 * k))) : t;
+}
+/* nt threads fill the image: nt is the workgroup size, a constant
+ * (fill_tbl4<THREADS>) or blockDim.x where the launch chooses it */
+template <class Q>
+__device__ __forceinline__ void fill_tbl4(uint32_t *lds, const uint32_t *te0, Q nt)
+{
+    uint4 *l4 = reinterpret_cast<uint4 *>(lds);
+    for (Q q = threadIdx.x; q < 8192; q += nt) {
+        const uint32_t v = tbl4_row(te0, q);
+        l4[q] = make_uint4(v, v, v, v);
+    }
+}
 template <int THREADS>
 __device__ __forceinline__ void fill_tbl4(uint32_t *lds, const uint32_t *te0)
 {
-    uint4 *l4 = reinterpret_cast<uint4 *>(lds);
-    for (int q = threadIdx.x; q < 8192; q += THREADS) {
-        const int r = q >> 12, x = (q >> 4) & 255, half = (q >> 3) & 1;
-        const int k = 2 * r + half;
-        const uint32_t t = te0[x];
-        const uint32_t v = k ? ((t << (8 * k)) | (t >> (32 - 8 * k))) : t;
-        l4[q] = make_uint4(v, v, v, v);
-    }
+    fill_tbl4(lds, te0, THREADS);
 }
 
 __device__ __forceinline__ void tbl4_lane_consts(uint32_t lane, uint32_t (&lk)[4])
@@ -150,6 +148,18 @@ __device__ __forceinline__ void tbl4_lane_consts(uint32_t lane, uint32_t (&lk)[4
  * in flight per wave); with at most 16 waves per CU (the 128 KiB table allows
  * one workgroup) that starves the LDS pipe.  gfx9 lgkmcnt still caps a wave at
  * 15 outstanding LDS ops. */
+template <int B, class TBL>
+__device__ __forceinline__ void issue_lookups4(TBL tbl, const uint32_t (&lk)[4], const uint32_t (&s)[B][4],
+                                               uint32_t (&a)[B][4][4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int b = 0; b < B; ++b)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[b][j][k] = lds_at(tbl, tt_addr(s[b][(j + k) & 3], lk[k], k));
+}
+
 template <int R0, int NR, int B, class TBL>
 __device__ __forceinline__ void enc_rounds4_from(TBL tbl, const uint32_t (&lk)[4], const otc_aes_key &K,
                                                  uint32_t (&s)[B][4])
@@ -158,13 +168,7 @@ __device__ __forceinline__ void enc_rounds4_from(TBL tbl, const uint32_t (&lk)[4
     for (int r = R0; r < NR; ++r) {
         uint32_t t[B][4];
         uint32_t a[B][4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int b = 0; b < B; ++b)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    a[b][j][k] = lds_at(tbl, tt_addr(s[b][(j + k) & 3], lk[k], k));
+        issue_lookups4(tbl, lk, s, a);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -177,13 +181,7 @@ __device__ __forceinline__ void enc_rounds4_from(TBL tbl, const uint32_t (&lk)[4
     }
     uint32_t t[B][4];
     uint32_t a[B][4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                a[b][j][k] = lds_at(tbl, tt_addr(s[b][(j + k) & 3], lk[k], k));
+    issue_lookups4(tbl, lk, s, a);
 #pragma unroll
     for (int b = 0; b < B; ++b) {
 #pragma unroll
@@ -210,15 +208,8 @@ __device__ __forceinline__ void fill_dtbl4(uint32_t *lds, const uint32_t *td0, c
 {
     uint4 *l4 = reinterpret_cast<uint4 *>(lds);
     for (int q = threadIdx.x; q < 8192 + 2048; q += THREADS) {
-        uint32_t v;
-        if (q < 8192) {
-            const int r = q >> 12, x = (q >> 4) & 255, half = (q >> 3) & 1;
-            const int k = 2 * r + half;
-            const uint32_t t = td0[x];
-            v = k ? ((t << (8 * k)) | (t >> (32 - 8 * k))) : t;
-        } else {
-            v = is4[(q - 8192) >> 3]; /* 8 uint4 (32 dwords) per 128-byte row */
-        }
+        /* past the four tables: 8 uint4 (32 dwords) per 128-byte row */
+        const uint32_t v = q < 8192 ? tbl4_row(td0, q) : is4[(q - 8192) >> 3];
         l4[q] = make_uint4(v, v, v, v);
     }
 }
@@ -266,9 +257,10 @@ __device__ __forceinline__ void dec_rounds4(TBL tbl, const uint32_t (&lk)[4], ui
         for (int j = 0; j < 4; ++j) s[b][j] = t[b][j];
 }
 
-__device__ __forceinline__ uint4 ld16(const uint8_t *p, uint64_t blk) { return ld_u4<false>(p + 16 * blk); }
-__device__ __forceinline__ void st16(uint8_t *p, uint64_t blk, uint4 v) { st_u4<false>(p + 16 * blk, v); }
-/* Streaming forms (otc_device.h ld_u4 / st_u4) for the kernels whose wave
+/* 16-byte block `blk` of a buffer (otc_device.h ld_u4 / st_u4), three ways:
+ * M_CACHED plain; M_STREAM and M_BATCH with the non-temporal bit by their
+ * build arms, M_BATCH also through the global address space.
+ * M_STREAM (the streaming form) is for the kernels whose wave
  * loads / stores 1 KiB of consecutive blocks per instruction -- ECB, CTR, the
  * CFB / CBC decryptions and their claim forms: the non-temporal bit
  * (OTC_TT_NT, default 1).  Round 6 A/B (profiles/r6/ntall_ab/, AES-256, 2
@@ -276,12 +268,33 @@ __device__ __forceinline__ void st16(uint8_t *p, uint64_t blk, uint4 v) { st_u4<
  * +1%, T-table CTR even.  NOT the serial segment chains: there each lane
  * walks its own segment 16 B at a time, the next block sits in the line just
  * read, and without the line in cache every block refetches it -- CBC
- * segment encryption fell from 1114-1120 to 472-476 GB/s with the bit. */
+ * segment encryption fell from 1114-1120 to 472-476 GB/s with the bit.
+ * M_BATCH is for the batch kernel's message buffers, which come from
+ * descriptors as plain addresses (otc_device.h ld_u4 on GLOBAL); the
+ * non-temporal bit (OTC_BATCH_NT, default 1) because each tile is read and
+ * written once, lane-linear.  Round 6 A/B, 3 reps (profiles/r6/batch_nt/):
+ * 1024 x 1 MiB packed 1484-1492 vs 1446-1460 GB/s, 16384 x 4 KiB packed
+ * 1156-1164 vs 1136-1144, 262144 x 4 KiB 1191-1212 vs 1173-1192, 65536 x
+ * 1504 B even. */
 #ifndef OTC_TT_NT
 #define OTC_TT_NT 1
 #endif
-__device__ __forceinline__ uint4 lds16(const uint8_t *p, uint64_t blk) { return ld_u4<OTC_TT_NT != 0>(p + 16 * blk); }
-__device__ __forceinline__ void sts16(uint8_t *p, uint64_t blk, uint4 v) { st_u4<OTC_TT_NT != 0>(p + 16 * blk, v); }
+#ifndef OTC_BATCH_NT
+#define OTC_BATCH_NT 1
+#endif
+enum Mem : int { M_CACHED, M_STREAM, M_BATCH };
+template <Mem M>
+constexpr bool MEM_NT = M == M_STREAM ? OTC_TT_NT != 0 : M == M_BATCH && OTC_BATCH_NT != 0;
+template <Mem M = M_CACHED>
+__device__ __forceinline__ uint4 ld16(const uint8_t *p, uint64_t blk)
+{
+    return ld_u4<MEM_NT<M>, M == M_BATCH>(p + 16 * blk);
+}
+template <Mem M = M_CACHED>
+__device__ __forceinline__ void st16(uint8_t *p, uint64_t blk, uint4 v)
+{
+    st_u4<MEM_NT<M>, M == M_BATCH>(p + 16 * blk, v);
+}
 enum : int { E_ECB = 0, E_CFB_DEC = 2, E_CFB_DEC_SEG = 3 };
 enum : int { D_ECB = 0, D_CBC = 1, D_CBC_SEG = 2 };
 
@@ -341,24 +354,60 @@ __device__ __forceinline__ auto tt_ref(const uint32_t *p)
         return p;
 }
 
-/* CLAIM: the T-table half of a co-resident split (otc_device.h SplitClaim):
+/* How a kernel of THREADS threads opens: the workgroup fills the encryption
+ * image, and each thread gets its lookup constants and its place.  (wave is
+ * not wave-uniform to hipcc: the kernels that need that take it through
+ * readfirstlane themselves.) */
+struct Place {
+    uint32_t lane, wave;
+};
+template <int THREADS>
+__device__ __forceinline__ Place tt_open(uint32_t *tbl, uint32_t (&lk)[4])
+{
+    fill_tbl4<THREADS>(tbl, g_tab.te0);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    tbl4_lane_consts(lane, lk);
+    return {lane, wave};
+}
+
+/* The T-table half of a co-resident split (otc_device.h SplitClaim):
  * workgroup 0 first runs the blocks past the last full 2048-block unit, then
- * every wave takes units from the back of the buffer until none are left. */
+ * every wave takes units from the back of the buffer until none are left.
+ * chunk(i0, full): the B blocks i0 + 64 b of a lane; full: all below nfull. */
+template <int B, int THREADS, class CHUNK>
+__device__ __forceinline__ void claim_walk(const SplitClaim &cl, uint64_t nfull, CHUNK chunk)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    strace(1);
+    /* the blocks past the last unit: workgroup 0, first */
+    const uint64_t done = (uint64_t)cl.nunits * CLAIM_UNIT;
+    if (blockIdx.x == 0) {
+        for (uint64_t base = done; base < nfull; base += (uint64_t)THREADS * B)
+            chunk(base + (uint64_t)wave * 64u * B + lane, false);
+    }
+    const uint32_t wg = blockIdx.x * (THREADS / 64u) + __builtin_amdgcn_readfirstlane(wave);
+    for (int64_t u = first_unit(cl, true, wg); u >= 0; u = claim_unit(cl, true)) {
+        const uint64_t u0 = (uint64_t)u * CLAIM_UNIT;
+#pragma unroll 1
+        for (uint32_t it = 0; it < CLAIM_UNIT / (64u * B); ++it) chunk(u0 + it * 64u * B + lane, true);
+    }
+    strace(5); /* trace builds: when the wave ran out of units (the claim tail) */
+}
+
 template <int NR, int MODE, int B, int THREADS, bool CLAIM>
 __device__ __forceinline__ void enc_tt_body(const EncParams &P, const otc_aes_key &K)
 {
     uint32_t *tbl = tt_lds<CLAIM, 2 * 256 * 64>();
-    fill_tbl4<THREADS>(tbl, g_tab.te0);
-    __syncthreads();
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
     uint32_t lk[4];
-    tbl4_lane_consts(lane, lk);
+    const auto [lane, wave] = tt_open<THREADS>(tbl, lk);
     constexpr uint64_t PER = (uint64_t)THREADS * B;
 
-    /* B blocks per lane: i0 + 64 b, b < B; `full`: all below lim (wave-uniform) */
-    auto chunk = [&](uint64_t i0, bool full, uint64_t lim) {
+    /* B blocks per lane: i0 + 64 b, b < B; `full`: all below nfull (wave-uniform) */
+    auto chunk = [&](uint64_t i0, bool full) {
+        const uint64_t lim = P.nfull;
         uint32_t s[B][4];
         uint4 x[B];
 #pragma unroll
@@ -366,20 +415,20 @@ __device__ __forceinline__ void enc_tt_body(const EncParams &P, const otc_aes_ke
             const uint64_t i = i0 + 64u * b;
             const bool ok = full || i < lim;
             if (MODE == E_ECB) {
-                uint4 v = ok ? lds16(P.in, i) : make_uint4(0, 0, 0, 0);
+                uint4 v = ok ? ld16<M_STREAM>(P.in, i) : make_uint4(0, 0, 0, 0);
                 s[b][0] = v.x; s[b][1] = v.y; s[b][2] = v.z; s[b][3] = v.w;
             } else if (MODE == E_CFB_DEC) { /* cipher input is the previous ciphertext */
-                x[b] = ok ? lds16(P.in, i) : make_uint4(0, 0, 0, 0);
+                x[b] = ok ? ld16<M_STREAM>(P.in, i) : make_uint4(0, 0, 0, 0);
                 uint4 v = (i == 0) ? make_uint4(P.iv[0], P.iv[1], P.iv[2], P.iv[3])
-                                   : (ok ? lds16(P.in, i - 1) : make_uint4(0, 0, 0, 0));
+                                   : (ok ? ld16<M_STREAM>(P.in, i - 1) : make_uint4(0, 0, 0, 0));
                 s[b][0] = v.x; s[b][1] = v.y; s[b][2] = v.z; s[b][3] = v.w;
             } else { /* CFB decrypt of independent segments: IV_s at segment starts */
-                x[b] = ok ? lds16(P.in, i) : make_uint4(0, 0, 0, 0);
+                x[b] = ok ? ld16<M_STREAM>(P.in, i) : make_uint4(0, 0, 0, 0);
                 const uint64_t sg = P.seg_shift < 64 ? (i >> P.seg_shift) : i / P.seg_blocks;
                 if (i == sg * P.seg_blocks) {
                     ctr_words(P.ctr, sg, false, s[b][0], s[b][1], s[b][2], s[b][3]);
                 } else {
-                    uint4 v = ok ? lds16(P.in, i - 1) : make_uint4(0, 0, 0, 0);
+                    uint4 v = ok ? ld16<M_STREAM>(P.in, i - 1) : make_uint4(0, 0, 0, 0);
                     s[b][0] = v.x; s[b][1] = v.y; s[b][2] = v.z; s[b][3] = v.w;
                 }
             }
@@ -398,29 +447,13 @@ __device__ __forceinline__ void enc_tt_body(const EncParams &P, const otc_aes_ke
             } else {
                 o = make_uint4(x[b].x ^ s[b][0], x[b].y ^ s[b][1], x[b].z ^ s[b][2], x[b].w ^ s[b][3]);
             }
-            if (full || i < lim) sts16(P.out, i, o);
+            if (full || i < lim) st16<M_STREAM>(P.out, i, o);
         }
     };
 
-    if constexpr (CLAIM) {
-        strace(1);
-        /* the blocks past the last unit: workgroup 0, first */
-        const uint64_t done = (uint64_t)P.cl.nunits * CLAIM_UNIT;
-        if (blockIdx.x == 0) {
-            for (uint64_t base = done; base < P.nfull; base += PER)
-                chunk(base + (uint64_t)wave * 64u * B + lane, false, P.nfull);
-        }
-        const uint32_t wg = blockIdx.x * (THREADS / 64u) + __builtin_amdgcn_readfirstlane(wave);
-        for (int64_t u = first_unit(P.cl, true, wg); u >= 0; u = claim_unit(P.cl, true)) {
-            const uint64_t u0 = (uint64_t)u * CLAIM_UNIT;
-#pragma unroll 1
-            for (uint32_t it = 0; it < CLAIM_UNIT / (64u * B); ++it) chunk(u0 + it * 64u * B + lane, true, 0);
-        }
-        strace(5); /* trace builds: when the wave ran out of units (the claim tail) */
-        return;
-    }
+    if constexpr (CLAIM) return claim_walk<B, THREADS>(P.cl, P.nfull, chunk);
     for (uint64_t base = (uint64_t)blockIdx.x * PER; base < P.nfull; base += (uint64_t)gridDim.x * PER)
-        chunk(base + (uint64_t)wave * 64u * B + lane, base + PER <= P.nfull, P.nfull);
+        chunk(base + (uint64_t)wave * 64u * B + lane, base + PER <= P.nfull);
 }
 
 template <int NR, int MODE, int B, int THREADS>
@@ -441,6 +474,17 @@ __global__ __launch_bounds__(THREADS) void k_aes_enc_tt(EncParams P, otc_aes_key
 #endif
 #ifndef OTC_TT_ECB_CLAIM_B
 #define OTC_TT_ECB_CLAIM_B OTC_TT_ENC_B
+#endif
+/* Negative control for the co-residency test (tests/test_gpu_queues.py):
+ * `make variant NAME=padclaim VFLAGS=-DOTC_DIAG_PAD_CLAIM` pads the T-table
+ * claim kernels' register descriptors to a 4-waves-per-SIMD budget -- what the
+ * round-4 static-LDS build did by accident -- so no bitsliced wave fits beside
+ * them and the split's halves run one after the other.  Never in the release
+ * build. */
+#ifdef OTC_DIAG_PAD_CLAIM
+#define OTC_CLAIM_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
+#else
+#define OTC_CLAIM_ATTR
 #endif
 template <int NR>
 __global__ __launch_bounds__(1024) OTC_CLAIM_ATTR void k_aes_ecb_tt_claim(EncParams P, otc_aes_key K)
@@ -484,6 +528,45 @@ struct CtrParams {
 
 __device__ __forceinline__ uint32_t te_u(uint32_t idx) { return g_tab.te0[idx & 0xFFu]; } /* uniform lookup */
 
+/* What a wave-iteration's blocks share: the wave-uniform words of rounds 1-2
+ * for the uniform counter C = chi:clo (its low 6 + log2(B) bits are 0) */
+struct CtrCache {
+    uint32_t U0, V0, V1, V2, V3;
+    uint32_t b15; /* low byte of C */
+};
+__device__ __forceinline__ CtrCache ctr_cache(uint64_t chi, uint64_t clo, const otc_aes_key &K)
+{
+    const uint32_t w0 = bswap32((uint32_t)(chi >> 32)) ^ K.rk[0];
+    const uint32_t w1 = bswap32((uint32_t)chi) ^ K.rk[1];
+    const uint32_t w2 = bswap32((uint32_t)(clo >> 32)) ^ K.rk[2];
+    const uint32_t w3u = bswap32((uint32_t)clo) ^ K.rk[3]; /* byte 15 (top byte) patched per block */
+    CtrCache C;
+    /* round 1, uniform parts */
+    C.U0 = te_u(w0) ^ rotl8(te_u(w1 >> 8)) ^ rotl16(te_u(w2 >> 16)) ^ K.rk[4];
+    const uint32_t t1 = te_u(w1) ^ rotl8(te_u(w2 >> 8)) ^ rotl16(te_u(w3u >> 16)) ^ rotl24(te_u(w0 >> 24)) ^ K.rk[5];
+    const uint32_t t2 = te_u(w2) ^ rotl8(te_u(w3u >> 8)) ^ rotl16(te_u(w0 >> 16)) ^ rotl24(te_u(w1 >> 24)) ^ K.rk[6];
+    const uint32_t t3 = te_u(w3u) ^ rotl8(te_u(w0 >> 8)) ^ rotl16(te_u(w1 >> 16)) ^ rotl24(te_u(w2 >> 24)) ^ K.rk[7];
+    /* round 2, uniform parts */
+    C.V0 = rotl8(te_u(t1 >> 8)) ^ rotl16(te_u(t2 >> 16)) ^ rotl24(te_u(t3 >> 24)) ^ K.rk[8];
+    C.V1 = te_u(t1) ^ rotl8(te_u(t2 >> 8)) ^ rotl16(te_u(t3 >> 16)) ^ K.rk[9];
+    C.V2 = te_u(t2) ^ rotl8(te_u(t3 >> 8)) ^ rotl24(te_u(t1 >> 24)) ^ K.rk[10];
+    C.V3 = te_u(t3) ^ rotl16(te_u(t1 >> 16)) ^ rotl24(te_u(t2 >> 24)) ^ K.rk[11];
+    C.b15 = (uint32_t)(clo & 0xFFu);
+    return C;
+}
+/* the state after round 2 of block (b, lane), whose counter is C + 64 b + lane */
+__device__ __forceinline__ void ctr_cache_block(const CtrCache &C, const otc_aes_key &K, const uint32_t *tbl,
+                                                const uint32_t (&lk)[4], int b, uint32_t lane, uint32_t (&s)[4])
+{
+    /* round 1: only T3[byte 15] varies */
+    const uint32_t c15 = (C.b15 | (uint32_t)(64 * b) | lane) ^ (K.rk[3] >> 24);
+    const uint32_t s0 = C.U0 ^ lds_at(tbl, (c15 << 8) | lk[3]);
+    /* round 2: the four lookups fed by s0 */
+    s[0] = C.V0 ^ lds_at(tbl, tt_addr(s0, lk[0], 0));
+    s[1] = C.V1 ^ lds_at(tbl, tt_addr(s0, lk[3], 3));
+    s[2] = C.V2 ^ lds_at(tbl, tt_addr(s0, lk[2], 2));
+    s[3] = C.V3 ^ lds_at(tbl, tt_addr(s0, lk[1], 1));
+}
 /* one wave-iteration: the 64 x B blocks from virtual block vw (uniform,
  * a multiple of 64 x B) */
 template <int NR, int B>
@@ -493,21 +576,7 @@ __device__ __forceinline__ void ctr_cached_iter(const CtrParams &P, const otc_ae
     /* uniform counter C = cbase + vw */
     uint64_t clo = P.cbase.lo + vw;
     uint64_t chi = P.cbase.hi + ((!P.wrap64 && clo < P.cbase.lo) ? 1u : 0u);
-    const uint32_t w0 = bswap32((uint32_t)(chi >> 32)) ^ K.rk[0];
-    const uint32_t w1 = bswap32((uint32_t)chi) ^ K.rk[1];
-    const uint32_t w2 = bswap32((uint32_t)(clo >> 32)) ^ K.rk[2];
-    const uint32_t w3u = bswap32((uint32_t)clo) ^ K.rk[3]; /* byte 15 (top byte) patched per block */
-    /* round 1, uniform parts */
-    const uint32_t U0 = te_u(w0) ^ rotl8(te_u(w1 >> 8)) ^ rotl16(te_u(w2 >> 16)) ^ K.rk[4];
-    const uint32_t t1 = te_u(w1) ^ rotl8(te_u(w2 >> 8)) ^ rotl16(te_u(w3u >> 16)) ^ rotl24(te_u(w0 >> 24)) ^ K.rk[5];
-    const uint32_t t2 = te_u(w2) ^ rotl8(te_u(w3u >> 8)) ^ rotl16(te_u(w0 >> 16)) ^ rotl24(te_u(w1 >> 24)) ^ K.rk[6];
-    const uint32_t t3 = te_u(w3u) ^ rotl8(te_u(w0 >> 8)) ^ rotl16(te_u(w1 >> 16)) ^ rotl24(te_u(w2 >> 24)) ^ K.rk[7];
-    /* round 2, uniform parts */
-    const uint32_t V0 = rotl8(te_u(t1 >> 8)) ^ rotl16(te_u(t2 >> 16)) ^ rotl24(te_u(t3 >> 24)) ^ K.rk[8];
-    const uint32_t V1 = te_u(t1) ^ rotl8(te_u(t2 >> 8)) ^ rotl16(te_u(t3 >> 16)) ^ K.rk[9];
-    const uint32_t V2 = te_u(t2) ^ rotl8(te_u(t3 >> 8)) ^ rotl24(te_u(t1 >> 24)) ^ K.rk[10];
-    const uint32_t V3 = te_u(t3) ^ rotl16(te_u(t1 >> 16)) ^ rotl24(te_u(t2 >> 24)) ^ K.rk[11];
-    const uint32_t b15 = (uint32_t)(clo & 0xFFu); /* low byte of C (low 6+log2(B) bits are 0) */
+    const CtrCache C = ctr_cache(chi, clo, K);
 
     const int64_t i0 = (int64_t)vw - (int64_t)P.shift + lane; /* real block index of (b=0, lane) */
     const bool full = vw >= P.shift && vw - P.shift + 64u * B <= P.nfull; /* uniform */
@@ -517,15 +586,8 @@ __device__ __forceinline__ void ctr_cached_iter(const CtrParams &P, const otc_ae
     for (int b = 0; b < B; ++b) {
         const int64_t i = i0 + 64 * b;
         const bool ok = full || (i >= 0 && (uint64_t)i < P.nfull);
-        x[b] = ok ? lds16(P.in, (uint64_t)i) : make_uint4(0, 0, 0, 0);
-        /* round 1: only T3[byte 15] varies */
-        const uint32_t c15 = (b15 | (uint32_t)(64 * b) | lane) ^ (K.rk[3] >> 24);
-        const uint32_t s0 = U0 ^ lds_at(tbl, (c15 << 8) | lk[3]);
-        /* round 2: the four lookups fed by s0 */
-        s[b][0] = V0 ^ lds_at(tbl, tt_addr(s0, lk[0], 0));
-        s[b][1] = V1 ^ lds_at(tbl, tt_addr(s0, lk[3], 3));
-        s[b][2] = V2 ^ lds_at(tbl, tt_addr(s0, lk[2], 2));
-        s[b][3] = V3 ^ lds_at(tbl, tt_addr(s0, lk[1], 1));
+        x[b] = ok ? ld16<M_STREAM>(P.in, (uint64_t)i) : make_uint4(0, 0, 0, 0);
+        ctr_cache_block(C, K, tbl, lk, b, lane, s[b]);
     }
     /* rounds 3..NR */
     enc_rounds4_from<3, NR, B>(tbl, lk, K, s);
@@ -535,9 +597,11 @@ __device__ __forceinline__ void ctr_cached_iter(const CtrParams &P, const otc_ae
         const int64_t i = i0 + 64 * b;
         const bool ok = full || (i >= 0 && (uint64_t)i < P.nfull);
         if (ok) {
-            sts16(P.out, (uint64_t)i,
-                 make_uint4(x[b].x ^ s[b][0], x[b].y ^ s[b][1], x[b].z ^ s[b][2], x[b].w ^ s[b][3]));
+            st16<M_STREAM>(P.out, (uint64_t)i,
+                           make_uint4(x[b].x ^ s[b][0], x[b].y ^ s[b][1], x[b].z ^ s[b][2], x[b].w ^ s[b][3]));
         } else if (i >= 0 && (uint64_t)i == P.nfull && P.tail) {
+            /* the partial last block (also written out in k_aes_ctr_batch_tt:
+             * as a shared helper it changed both kernels' loop instructions) */
             const uint32_t ks[4] = {s[b][0], s[b][1], s[b][2], s[b][3]};
             for (uint32_t n = 0; n < P.tail; ++n)
                 P.out[16 * (uint64_t)i + n] = P.in[16 * (uint64_t)i + n] ^ (uint8_t)(ks[n >> 2] >> (8 * (n & 3)));
@@ -549,13 +613,9 @@ template <int NR, int B, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_aes_ctr_tt_cached(CtrParams P, otc_aes_key K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tbl[2 * 256 * 64];
-    fill_tbl4<THREADS>(tbl, g_tab.te0);
-    __syncthreads();
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t lk[4];
-    tbl4_lane_consts(lane, lk);
+    const uint32_t lane = tt_open<THREADS>(tbl, lk).lane;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr uint64_t PER = (uint64_t)THREADS * B;
     const uint64_t vtotal = P.nfull + (P.tail ? 1u : 0u) + P.shift;
     for (uint64_t vbase = (uint64_t)blockIdx.x * PER; vbase < vtotal; vbase += (uint64_t)gridDim.x * PER)
@@ -575,12 +635,9 @@ __global__ __launch_bounds__(1024) void k_aes_ctr_tt_persist(CtrParams P, otc_ae
 {
     constexpr int B = OTC_TT_CTR_B;
     __shared__ __attribute__((aligned(16))) uint32_t tbl[2 * 256 * 64];
-    fill_tbl4<1024>(tbl, g_tab.te0);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t lk[4];
-    tbl4_lane_consts(lane, lk);
+    const uint32_t lane = tt_open<1024>(tbl, lk).lane;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int64_t u = first_unit(P.cl, true, blockIdx.x * 16u + wave); u >= 0; u = claim_unit(P.cl, true)) {
 #pragma unroll 1
         for (uint32_t it = 0; it < CLAIM_UNIT / (64u * B); ++it)
@@ -613,26 +670,19 @@ __device__ __forceinline__ void dec_tt_body(const DecParams &P, const otc_aes_ke
         for (int b = 0; b < B; ++b) {
             const uint64_t i = i0 + 64u * b;
             const bool ok = full || i < P.nfull;
-            uint4 v = ok ? lds16(P.in, i) : make_uint4(0, 0, 0, 0);
+            uint4 v = ok ? ld16<M_STREAM>(P.in, i) : make_uint4(0, 0, 0, 0);
             s[b][0] = v.x ^ K.rk[0]; s[b][1] = v.y ^ K.rk[1];
             s[b][2] = v.z ^ K.rk[2]; s[b][3] = v.w ^ K.rk[3];
             if (MODE == D_CBC || MODE == D_CBC_SEG) {
-                bool first;
-                Ctr128 ivv = P.iv;
-                if (MODE == D_CBC) {
-                    first = (i == 0);
-                } else {
-                    first = (i & ((1ull << P.seg_shift) - 1)) == 0;
-                    const uint64_t seg = i >> P.seg_shift;
-                    ivv.lo = P.iv.lo + seg;
-                    ivv.hi = P.iv.hi + (ivv.lo < P.iv.lo ? 1 : 0);
-                }
+                /* a segment's first block takes IV_seg = iv + seg */
+                const uint64_t seg = MODE == D_CBC ? 0 : i >> P.seg_shift;
+                const bool first = MODE == D_CBC ? i == 0 : (i & ((1ull << P.seg_shift) - 1)) == 0;
                 if (first) {
                     uint32_t w0, w1, w2, w3;
-                    ctr_words(ivv, 0, false, w0, w1, w2, w3);
+                    ctr_words(P.iv, seg, false, w0, w1, w2, w3);
                     prev[b] = make_uint4(w0, w1, w2, w3);
                 } else {
-                    prev[b] = ok ? lds16(P.in, i - 1) : make_uint4(0, 0, 0, 0);
+                    prev[b] = ok ? ld16<M_STREAM>(P.in, i - 1) : make_uint4(0, 0, 0, 0);
                 }
             }
         }
@@ -646,23 +696,11 @@ __device__ __forceinline__ void dec_tt_body(const DecParams &P, const otc_aes_ke
             if (MODE != D_ECB) {
                 o.x ^= prev[b].x; o.y ^= prev[b].y; o.z ^= prev[b].z; o.w ^= prev[b].w;
             }
-            if (full || i < P.nfull) sts16(P.out, i, o);
+            if (full || i < P.nfull) st16<M_STREAM>(P.out, i, o);
         }
     };
 
-    if constexpr (CLAIM) { /* as k_aes_enc_tt */
-        strace(1);
-        const uint64_t done = (uint64_t)P.cl.nunits * CLAIM_UNIT;
-        if (blockIdx.x == 0)
-            for (uint64_t base = done; base < P.nfull; base += PER) chunk(base + (uint64_t)wave * 64u * B + lane, false);
-        const uint32_t wg = blockIdx.x * (THREADS / 64u) + __builtin_amdgcn_readfirstlane(wave);
-        for (int64_t u = first_unit(P.cl, true, wg); u >= 0; u = claim_unit(P.cl, true)) {
-#pragma unroll 1
-            for (uint32_t it = 0; it < CLAIM_UNIT / (64u * B); ++it) chunk((uint64_t)u * CLAIM_UNIT + it * 64u * B + lane, true);
-        }
-        strace(5);
-        return;
-    }
+    if constexpr (CLAIM) return claim_walk<B, THREADS>(P.cl, P.nfull, chunk);
     for (uint64_t base = (uint64_t)blockIdx.x * PER; base < P.nfull; base += (uint64_t)gridDim.x * PER)
         chunk(base + (uint64_t)wave * 64u * B + lane, base + PER <= P.nfull);
 }
@@ -725,13 +763,8 @@ template <int NR, int B, int THREADS, bool CFB = false>
 __global__ __launch_bounds__(THREADS) void k_aes_cbc_enc_seg(CbcSegParams P, otc_aes_key K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tbl[2 * 256 * 64];
-    fill_tbl4<THREADS>(tbl, g_tab.te0);
-    __syncthreads();
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
     uint32_t lk[4];
-    tbl4_lane_consts(lane, lk);
+    const auto [lane, wave] = tt_open<THREADS>(tbl, lk);
     constexpr uint64_t PER = (uint64_t)THREADS * B;
 
     for (uint64_t base = (uint64_t)blockIdx.x * PER; base < P.nseg; base += (uint64_t)gridDim.x * PER) {
@@ -743,10 +776,7 @@ __global__ __launch_bounds__(THREADS) void k_aes_cbc_enc_seg(CbcSegParams P, otc
         for (int b = 0; b < B; ++b) {
             seg[b] = base + (uint64_t)wave * 64u * B + 64u * b + lane;
             live[b] = seg[b] < P.nseg;
-            Ctr128 ivv;
-            ivv.lo = P.iv0.lo + seg[b];
-            ivv.hi = P.iv0.hi + (ivv.lo < P.iv0.lo ? 1 : 0);
-            ctr_words(ivv, 0, false, c[b][0], c[b][1], c[b][2], c[b][3]);
+            ctr_words(P.iv0, seg[b], false, c[b][0], c[b][1], c[b][2], c[b][3]);
             nxt[b] = (live[b] && P.seg_blocks) ? ld16(P.in, seg[b] * P.seg_blocks) : make_uint4(0, 0, 0, 0);
         }
         for (uint64_t j = 0; j < P.seg_blocks; ++j) {
@@ -787,10 +817,7 @@ __device__ __forceinline__ void seg_chain_g(const CbcSegParams &P, const otc_aes
     const uint64_t first = seg * sb; /* block index of the segment's first block */
     uint32_t c[4];
     uint4 cur[G], nxt[DB ? G : 1];
-    Ctr128 ivv;
-    ivv.lo = P.iv0.lo + seg;
-    ivv.hi = P.iv0.hi + (ivv.lo < P.iv0.lo ? 1 : 0);
-    ctr_words(ivv, 0, false, c[0], c[1], c[2], c[3]);
+    ctr_words(P.iv0, seg, false, c[0], c[1], c[2], c[3]);
 #pragma unroll
     for (int t = 0; t < G; ++t) cur[t] = (live && ng) ? ld16(P.in, first + t) : make_uint4(0, 0, 0, 0);
     for (uint64_t g = 0; g < ng; ++g) {
@@ -835,23 +862,16 @@ __device__ __forceinline__ void seg_chain_g(const CbcSegParams &P, const otc_aes
 /* One chain per thread; the workgroup size is chosen at launch (a multiple
  * of 64 up to THREADS): with fewer chains than CUs x THREADS the launch
  * shrinks the workgroups so that every CU gets chains, instead of filling
- * nseg / THREADS CUs and leaving the rest idle (launch_seg_nr). */
+ * nseg / THREADS CUs and leaving the rest idle (launch_seg). */
 template <int NR, int THREADS, int G, bool CFB = false>
 __global__ __launch_bounds__(THREADS) void k_aes_cbc_enc_seg_g(CbcSegParams P, otc_aes_key K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tbl[2 * 256 * 64];
     const uint32_t nt = blockDim.x;
-    if (nt == THREADS) {
+    if (nt == THREADS)
         fill_tbl4<THREADS>(tbl, g_tab.te0);
-    } else {
-        uint4 *l4 = reinterpret_cast<uint4 *>(tbl);
-        for (uint32_t q = threadIdx.x; q < 8192; q += nt) {
-            const uint32_t r = q >> 12, x = (q >> 4) & 255, half = (q >> 3) & 1, k = 2 * r + half;
-            const uint32_t t = g_tab.te0[x];
-            const uint32_t v = k ? ((t << (8 * k)) | (t >> (32 - 8 * k))) : t;
-            l4[q] = make_uint4(v, v, v, v);
-        }
-    }
+    else
+        fill_tbl4(tbl, g_tab.te0, nt);
     __syncthreads();
     uint32_t lk[4];
     tbl4_lane_consts(threadIdx.x & 63u, lk);
@@ -869,10 +889,8 @@ template <int NR, int G, bool CFB>
 __global__ __launch_bounds__(1024) OTC_CLAIM_ATTR void k_aes_seg_enc_tt_claim(CbcSegParams P, otc_aes_key K)
 {
     uint32_t *tbl = tt_lds<true, 2 * 256 * 64>();
-    fill_tbl4<1024>(tbl, g_tab.te0);
-    __syncthreads();
     uint32_t lk[4];
-    tbl4_lane_consts(threadIdx.x & 63u, lk);
+    tt_open<1024>(tbl, lk);
     strace(1);
     const uint64_t done = (uint64_t)P.cl.nunits * SEG_UNIT;
     if (blockIdx.x == 0 && done + (threadIdx.x & ~63u) < P.nseg) { /* the remainder (< 64 segments): wave 0 */
@@ -893,11 +911,8 @@ __global__ __launch_bounds__(256) void k_cbc_seg_fixup(const uint8_t *in, uint8_
     const uint64_t s = 1 + (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= nseg) return;
     const uint64_t i = s * seg_blocks;
-    Ctr128 ivv;
-    ivv.lo = iv0.lo + s;
-    ivv.hi = iv0.hi + (ivv.lo < iv0.lo ? 1 : 0);
     uint32_t w0, w1, w2, w3;
-    ctr_words(ivv, 0, false, w0, w1, w2, w3);
+    ctr_words(iv0, s, false, w0, w1, w2, w3);
     const uint4 prev = ld16(in, i - 1);
     uint4 o = ld16(out, i);
     o.x ^= prev.x ^ w0; o.y ^= prev.y ^ w1; o.z ^= prev.z ^ w2; o.w ^= prev.w ^ w3;
@@ -930,13 +945,8 @@ template <int NR, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_aes_ctr_shift(CtrShiftParams P, otc_aes_key K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tbl[2 * 256 * 64];
-    fill_tbl4<THREADS>(tbl, g_tab.te0);
-    __syncthreads();
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
     uint32_t lk[4];
-    tbl4_lane_consts(lane, lk);
+    const auto [lane, wave] = tt_open<THREADS>(tbl, lk);
     constexpr uint64_t WPB = THREADS / 64;
     const uint64_t nchunks = (P.a + P.len + 15) / 16;
     const uint32_t d = 16u - P.a, dq = d >> 2, db = d & 3u;
@@ -1021,45 +1031,18 @@ typedef const __attribute__((address_space(4))) uint32_t *cptr32;
 typedef const __attribute__((address_space(4))) uint64_t *cptr64;
 __device__ __forceinline__ uint32_t cld32(const uint32_t *p) { return *(cptr32)p; }
 __device__ __forceinline__ uint64_t cld64(const uint64_t *p) { return *(cptr64)p; }
-/* message buffers come from descriptors as plain addresses: access them as
- * GLOBAL memory, or hipcc emits flat_* ops, which count against lgkmcnt and
- * make every LDS wait also wait for HBM */
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+/* the message buffers come from descriptors as plain addresses: GLOBAL
+ * memory to the 16-byte accesses (ld16 / st16 <M_BATCH>) and to the bytes
+ * of a partial last block */
 typedef __attribute__((address_space(1))) uint8_t g_u8;
-/* OTC_BATCH_NT (default 1): the non-temporal bit on the message loads /
- * stores -- each tile is read and written once, lane-linear.  Round 6 A/B,
- * 3 reps (profiles/r6/batch_nt/): 1024 x 1 MiB packed 1484-1492 vs 1446-1460
- * GB/s, 16384 x 4 KiB packed 1156-1164 vs 1136-1144, 262144 x 4 KiB
- * 1191-1212 vs 1173-1192, 65536 x 1504 B even. */
-#ifndef OTC_BATCH_NT
-#define OTC_BATCH_NT 1
-#endif
-__device__ __forceinline__ uint4 gld16(const uint8_t *p, uint64_t blk)
-{
-    const g_u32x4 *q = (const g_u32x4 *)(p + 16 * blk);
-    const u32x4 v = OTC_BATCH_NT ? __builtin_nontemporal_load(q) : *q;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void gst16(uint8_t *p, uint64_t blk, uint4 v)
-{
-    g_u32x4 *q = (g_u32x4 *)(p + 16 * blk);
-    const u32x4 w = {v.x, v.y, v.z, v.w};
-    if (OTC_BATCH_NT) __builtin_nontemporal_store(w, q);
-    else *q = w;
-}
 
 template <int NR, int B, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_aes_ctr_batch_tt(BatchParams P)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tbl[2 * 256 * 64];
-    fill_tbl4<THREADS>(tbl, g_tab.te0);
-    __syncthreads();
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = ufl(threadIdx.x >> 6);
     uint32_t lk[4];
-    tbl4_lane_consts(lane, lk);
+    const uint32_t lane = tt_open<THREADS>(tbl, lk).lane;
+    const uint32_t wave = ufl(threadIdx.x >> 6);
     constexpr uint32_t WAVES = THREADS / 64;
     constexpr uint64_t TILE = 64u * B;
 
@@ -1118,6 +1101,10 @@ __global__ __launch_bounds__(THREADS) void k_aes_ctr_batch_tt(BatchParams P)
             const uint64_t cb = c.lo - shift; /* no borrow: shift <= ctr0.lo mod TILE */
             const uint64_t clo = cb + vb;
             const uint64_t chi = c.hi + (clo < cb ? 1u : 0u);
+            /* ctr_cache(chi, clo, K), written out: through the call hipcc
+             * compiles the three B = 4 kernels differently (-182 to +5
+             * instructions, same registers), and AES-128 at 16384 x 4 KiB
+             * then fell below the written-out form's range (docs/PERF.md) */
             const uint32_t w0 = bswap32((uint32_t)(chi >> 32)) ^ K.rk[0];
             const uint32_t w1 = bswap32((uint32_t)chi) ^ K.rk[1];
             const uint32_t w2 = bswap32((uint32_t)(clo >> 32)) ^ K.rk[2];
@@ -1131,17 +1118,13 @@ __global__ __launch_bounds__(THREADS) void k_aes_ctr_batch_tt(BatchParams P)
             const uint32_t V2 = te_u(t2) ^ rotl8(te_u(t3 >> 8)) ^ rotl24(te_u(t1 >> 24)) ^ K.rk[10];
             const uint32_t V3 = te_u(t3) ^ rotl16(te_u(t1 >> 16)) ^ rotl24(te_u(t2 >> 24)) ^ K.rk[11];
             const uint32_t b15 = (uint32_t)(clo & 0xFFu);
+            const CtrCache C{U0, V0, V1, V2, V3, b15};
             i0 = (int64_t)vb - (int64_t)shift + lane;
 #pragma unroll
             for (int b = 0; b < B; ++b) {
                 const int64_t i = i0 + 64 * b;
-                x[b] = (i >= 0 && (uint64_t)i < nfull) ? gld16(in, (uint64_t)i) : make_uint4(0, 0, 0, 0);
-                const uint32_t c15 = (b15 | (uint32_t)(64 * b) | lane) ^ (K.rk[3] >> 24);
-                const uint32_t s0 = U0 ^ lds_at(tbl, (c15 << 8) | lk[3]);
-                s[b][0] = V0 ^ lds_at(tbl, tt_addr(s0, lk[0], 0));
-                s[b][1] = V1 ^ lds_at(tbl, tt_addr(s0, lk[3], 3));
-                s[b][2] = V2 ^ lds_at(tbl, tt_addr(s0, lk[2], 2));
-                s[b][3] = V3 ^ lds_at(tbl, tt_addr(s0, lk[1], 1));
+                x[b] = (i >= 0 && (uint64_t)i < nfull) ? ld16<M_BATCH>(in, (uint64_t)i) : make_uint4(0, 0, 0, 0);
+                ctr_cache_block(C, K, tbl, lk, b, lane, s[b]);
             }
             enc_rounds4_from<3, NR, B>(tbl, lk, K, s);
         } else {
@@ -1150,7 +1133,7 @@ __global__ __launch_bounds__(THREADS) void k_aes_ctr_batch_tt(BatchParams P)
             for (int b = 0; b < B; ++b) {
                 const uint64_t i = (uint64_t)i0 + 64u * b;
                 ctr_words(c, i, false, s[b][0], s[b][1], s[b][2], s[b][3]);
-                x[b] = i < nfull ? gld16(in, i) : make_uint4(0, 0, 0, 0);
+                x[b] = i < nfull ? ld16<M_BATCH>(in, i) : make_uint4(0, 0, 0, 0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) s[b][j] ^= K.rk[j];
             }
@@ -1161,7 +1144,7 @@ __global__ __launch_bounds__(THREADS) void k_aes_ctr_batch_tt(BatchParams P)
             const int64_t i = i0 + 64 * b;
             if (i < 0) continue;
             if ((uint64_t)i < nfull) {
-                gst16(out, (uint64_t)i,
+                st16<M_BATCH>(out, (uint64_t)i,
                       make_uint4(x[b].x ^ s[b][0], x[b].y ^ s[b][1], x[b].z ^ s[b][2], x[b].w ^ s[b][3]));
             } else if ((uint64_t)i == nfull && tail) {
                 const uint32_t ks[4] = {s[b][0], s[b][1], s[b][2], s[b][3]};
@@ -1241,98 +1224,77 @@ constexpr int DEC_B = OTC_TT_DEC_B;
 constexpr int SEG_THREADS = 1024;
 constexpr int SEG_B = 2;
 
-template <int NR, int MODE, int T, int B>
-hipError_t launch_enc_tb(const EncParams &P, const otc_aes_key &K, hipStream_t st)
+/* f(threads, blocks per lane) as constants: small_shape's pick, the bulk
+ * shape being T x B */
+template <int T, int B, class F>
+hipError_t with_shape(uint64_t nblocks, F f)
 {
-    int grid = grid_for(P.nfull, (uint64_t)T * B, 1); /* 128 KiB LDS: one workgroup per CU */
-    hipLaunchKernelGGL((k_aes_enc_tt<NR, MODE, B, T>), dim3(grid), dim3(T), 0, st, P, K);
-    return hipGetLastError();
-}
-
-template <int NR, int MODE>
-hipError_t launch_enc_nr(const EncParams &P, const otc_aes_key &K, hipStream_t st)
-{
-    switch (small_shape(P.nfull)) {
-    case SHAPE_256x1: return launch_enc_tb<NR, MODE, 256, 1>(P, K, st);
-    case SHAPE_1024x1: return launch_enc_tb<NR, MODE, 1024, 1>(P, K, st);
-    default: return launch_enc_tb<NR, MODE, ENC_THREADS, ENC_B>(P, K, st);
+    using std::integral_constant;
+    switch (small_shape(nblocks)) {
+    case SHAPE_256x1: return f(integral_constant<int, 256>{}, integral_constant<int, 1>{});
+    case SHAPE_1024x1: return f(integral_constant<int, 1024>{}, integral_constant<int, 1>{});
+    default: return f(integral_constant<int, T>{}, integral_constant<int, B>{});
     }
 }
+using otc_impl::with_rounds;
 
 template <int MODE>
 hipError_t launch_enc(const EncParams &P, const otc_aes_key &K, hipStream_t st)
 {
-    switch (K.nr) {
-    case 10: return launch_enc_nr<10, MODE>(P, K, st);
-    case 12: return launch_enc_nr<12, MODE>(P, K, st);
-    case 14: return launch_enc_nr<14, MODE>(P, K, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int NR, int MODE>
-hipError_t launch_dec_nr(const DecParams &P, const otc_aes_key &K, hipStream_t st)
-{
-    switch (small_shape(P.nfull)) {
-    case SHAPE_256x1:
-        hipLaunchKernelGGL((k_aes_dec_tt<NR, MODE, 1, 256>), dim3(grid_for(P.nfull, 256, 1)), dim3(256), 0, st, P, K);
-        break;
-    case SHAPE_1024x1:
-        hipLaunchKernelGGL((k_aes_dec_tt<NR, MODE, 1, 1024>), dim3(grid_for(P.nfull, 1024, 1)), dim3(1024), 0, st, P,
-                           K);
-        break;
-    default:
-        hipLaunchKernelGGL((k_aes_dec_tt<NR, MODE, DEC_B, DEC_THREADS>),
-                           dim3(grid_for(P.nfull, (uint64_t)DEC_THREADS * DEC_B, 1)), dim3(DEC_THREADS), 0, st, P, K);
-    }
-    return hipGetLastError();
+    return with_rounds(K.nr, [&](auto nr) {
+        return with_shape<ENC_THREADS, ENC_B>(P.nfull, [&](auto t, auto b) {
+            constexpr int NR = decltype(nr)::value, T = decltype(t)::value, B = decltype(b)::value;
+            const int grid = grid_for(P.nfull, (uint64_t)T * B, 1); /* 128 KiB LDS: one workgroup per CU */
+            hipLaunchKernelGGL((k_aes_enc_tt<NR, MODE, B, T>), dim3(grid), dim3(T), 0, st, P, K);
+            return hipGetLastError();
+        });
+    });
 }
 
 template <int MODE>
 hipError_t launch_dec(const DecParams &P, const otc_aes_key &K, hipStream_t st)
 {
-    switch (K.nr) {
-    case 10: return launch_dec_nr<10, MODE>(P, K, st);
-    case 12: return launch_dec_nr<12, MODE>(P, K, st);
-    case 14: return launch_dec_nr<14, MODE>(P, K, st);
-    default: return hipErrorInvalidValue;
-    }
+    return with_rounds(K.nr, [&](auto nr) {
+        return with_shape<DEC_THREADS, DEC_B>(P.nfull, [&](auto t, auto b) {
+            constexpr int NR = decltype(nr)::value, T = decltype(t)::value, B = decltype(b)::value;
+            const int grid = grid_for(P.nfull, (uint64_t)T * B, 1); /* 160 KiB LDS: one workgroup per CU */
+            hipLaunchKernelGGL((k_aes_dec_tt<NR, MODE, B, T>), dim3(grid), dim3(T), 0, st, P, K);
+            return hipGetLastError();
+        });
+    });
 }
 
 /* the T-table half of a claimed split: one persistent workgroup per CU */
+inline dim3 claim_grid(const SplitClaim &cl) { return dim3(cl.wgs ? cl.wgs : (unsigned)num_cus()); }
+
 template <int MODE>
 hipError_t launch_enc_claim(const EncParams &P, const otc_aes_key &K, hipStream_t st)
 {
-    const dim3 g(P.cl.wgs ? P.cl.wgs : (unsigned)num_cus()), b(ENC_THREADS);
-    auto go = [&](auto nr) {
+    const dim3 g = claim_grid(P.cl), b(ENC_THREADS);
+    return with_rounds(K.nr, [&](auto nr) {
         constexpr int NR = decltype(nr)::value;
         if constexpr (MODE == E_ECB) return launch_dyn<k_aes_ecb_tt_claim<NR>>(g, b, ENC_LDS, st, P, K);
         else if constexpr (MODE == E_CFB_DEC) return launch_dyn<k_aes_cfb_tt_claim<NR>>(g, b, ENC_LDS, st, P, K);
         else return launch_dyn<k_aes_cfbseg_tt_claim<NR>>(g, b, ENC_LDS, st, P, K);
-    };
-    switch (K.nr) {
-    case 10: return go(std::integral_constant<int, 10>{});
-    case 12: return go(std::integral_constant<int, 12>{});
-    case 14: return go(std::integral_constant<int, 14>{});
-    default: return hipErrorInvalidValue;
-    }
+    });
 }
 
 template <int MODE>
 hipError_t launch_dec_claim(const DecParams &P, const otc_aes_key &K, hipStream_t st)
 {
-    const dim3 g(P.cl.wgs ? P.cl.wgs : (unsigned)num_cus()), b(DEC_THREADS);
-    switch (K.nr) {
-    case 10: return launch_dyn<k_aes_dec_tt_claim<10, MODE>>(g, b, DEC_LDS, st, P, K);
-    case 12: return launch_dyn<k_aes_dec_tt_claim<12, MODE>>(g, b, DEC_LDS, st, P, K);
-    case 14: return launch_dyn<k_aes_dec_tt_claim<14, MODE>>(g, b, DEC_LDS, st, P, K);
-    default: return hipErrorInvalidValue;
-    }
+    const dim3 g = claim_grid(P.cl), b(DEC_THREADS);
+    return with_rounds(K.nr, [&](auto nr) {
+        return launch_dyn<k_aes_dec_tt_claim<decltype(nr)::value, MODE>>(g, b, DEC_LDS, st, P, K);
+    });
 }
 
+/* segment encryption: the persistent claim kernel (64-segment units from the
+ * back of P.cl, P.cl.wgs workgroups, default one per CU), or the grid */
 template <int NR, bool CFB>
-hipError_t launch_seg_nr(const CbcSegParams &P, const otc_aes_key &K, hipStream_t st)
+hipError_t launch_seg(const CbcSegParams &P, const otc_aes_key &K, bool claimed, hipStream_t st)
 {
+    if (claimed)
+        return launch_dyn<k_aes_seg_enc_tt_claim<NR, SEG_CLAIM_G, CFB>>(claim_grid(P.cl), dim3(1024), ENC_LDS, st, P, K);
     int grid = grid_for(P.nseg, (uint64_t)SEG_THREADS * SEG_B, 1);
     /* 8-block load/store bursts per segment (+119% over one block at a time,
      * profiles/r1/otbench_cbcenc_group_ab.jsonl); B = 1: two 8-block buffers
@@ -1355,23 +1317,12 @@ hipError_t launch_seg_nr(const CbcSegParams &P, const otc_aes_key &K, hipStream_
 }
 
 template <int NR, int B>
-hipError_t launch_ctr_batch_nrb(const BatchParams &P, hipStream_t st)
+hipError_t launch_ctr_batch(const BatchParams &P, hipStream_t st)
 {
     /* one workgroup per CU (128 KiB LDS), 16 tiles per workgroup step */
     const int grid = grid_for(P.ntiles, BATCH_THREADS / 64, 1);
     hipLaunchKernelGGL((k_aes_ctr_batch_tt<NR, B, BATCH_THREADS>), dim3(grid), dim3(BATCH_THREADS), 0, st, P);
     return hipGetLastError();
-}
-
-template <int NR>
-hipError_t launch_ctr_batch_nr(const BatchParams &P, int tile_blocks, hipStream_t st)
-{
-    switch (tile_blocks) {
-    case 64: return launch_ctr_batch_nrb<NR, 1>(P, st);
-    case 128: return launch_ctr_batch_nrb<NR, 2>(P, st);
-    case 256: return launch_ctr_batch_nrb<NR, 4>(P, st);
-    default: return hipErrorInvalidValue;
-    }
 }
 
 } // namespace
@@ -1389,12 +1340,15 @@ hipError_t tt_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const 
 {
     BatchParams P{msgs, keys, tile_msg, tile_first, ntiles};
     if (cl) P.cl = *cl;
-    switch (nr) {
-    case 10: return launch_ctr_batch_nr<10>(P, tile_blocks, st);
-    case 12: return launch_ctr_batch_nr<12>(P, tile_blocks, st);
-    case 14: return launch_ctr_batch_nr<14>(P, tile_blocks, st);
-    default: return hipErrorInvalidValue;
-    }
+    return with_rounds(nr, [&](auto r) {
+        constexpr int NR = decltype(r)::value;
+        switch (tile_blocks) {
+        case 64: return launch_ctr_batch<NR, 1>(P, st);
+        case 128: return launch_ctr_batch<NR, 2>(P, st);
+        case 256: return launch_ctr_batch<NR, 4>(P, st);
+        default: return hipErrorInvalidValue;
+        }
+    });
 }
 
 /* a job's parameter blocks: the encryption-direction kernels' (ECB
@@ -1468,30 +1422,9 @@ hipError_t tt_claim(const Job &j, SplitClaim cl, hipStream_t st)
     return hipErrorInvalidValue;
 }
 
-/* one 1024- or 256-thread workgroup per CU (the 128 KiB 4-table image) */
-template <int NR, int T, int B>
-hipError_t launch_ctr_cached_tb(CtrParams P, const otc_aes_key &K, uint64_t ctr_lo, hipStream_t st)
-{
-    constexpr uint64_t PER = (uint64_t)T * B;
-    P.shift = ctr_lo & (PER - 1);
-    P.cbase.lo = ctr_lo - P.shift;
-    const uint64_t vt = P.nfull + (P.tail ? 1 : 0) + P.shift;
-    hipLaunchKernelGGL((k_aes_ctr_tt_cached<NR, B, T>), dim3(grid_for(vt, PER, 1)), dim3(T), 0, st, P, K);
-    return hipGetLastError();
-}
-
-template <int NR>
-hipError_t launch_ctr_cached(CtrParams P, const otc_aes_key &K, uint64_t ctr_lo, hipStream_t st)
-{
-    switch (small_shape(P.nfull + (P.tail ? 1 : 0))) {
-    case SHAPE_256x1: return launch_ctr_cached_tb<NR, 256, 1>(P, K, ctr_lo, st);
-    case SHAPE_1024x1: return launch_ctr_cached_tb<NR, 1024, 1>(P, K, ctr_lo, st);
-    default: return launch_ctr_cached_tb<NR, 1024, OTC_TT_CTR_B>(P, K, ctr_lo, st);
-    }
-}
-
-/* all of CtrParams but the launch shape's part (shift, cbase.lo) */
-static CtrParams ctr_params(const void *in, void *out, size_t nbytes, Ctr128 c, bool wrap64)
+/* CtrParams for a launch whose wave-iterations are aligned to `per` blocks
+ * (a power of two: the shape's threads x blocks per lane) */
+static CtrParams ctr_params(const void *in, void *out, size_t nbytes, Ctr128 c, bool wrap64, uint64_t per)
 {
     CtrParams P{};
     P.in = (const uint8_t *)in;
@@ -1499,50 +1432,45 @@ static CtrParams ctr_params(const void *in, void *out, size_t nbytes, Ctr128 c, 
     P.nfull = nbytes / 16;
     P.tail = (uint32_t)(nbytes % 16);
     P.wrap64 = wrap64 ? 1u : 0u;
+    P.shift = c.lo & (per - 1);
     P.cbase.hi = c.hi;
+    P.cbase.lo = c.lo - P.shift;
     return P;
 }
 
-hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
-                  hipStream_t st)
-{
-    const CtrParams P = ctr_params(in, out, nbytes, c, wrap64);
-    switch (K.nr) {
-    case 10: return launch_ctr_cached<10>(P, K, c.lo, st);
-    case 12: return launch_ctr_cached<12>(P, K, c.lo, st);
-    case 14: return launch_ctr_cached<14>(P, K, c.lo, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-/* the persistent claim form of tt_ctr: its virtual range (the blocks plus
- * ctr0 mod the bulk shape's step in front) in 2048-block units */
+/* the persistent claim form's virtual range (the blocks plus ctr0 mod the
+ * bulk shape's step in front) in 2048-block units */
 constexpr uint64_t CTR_BULK_PER = 1024ull * OTC_TT_CTR_B; /* as the grid kernel's bulk shape */
 uint64_t tt_ctr_claim_units(size_t nbytes, uint64_t ctr_lo)
 {
     return (nbytes / 16 + (nbytes % 16 ? 1 : 0) + (ctr_lo & (CTR_BULK_PER - 1)) + CLAIM_UNIT - 1) / CLAIM_UNIT;
 }
 
-hipError_t tt_ctr_claim(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
-                        SplitClaim cl, hipStream_t st)
+hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
+                  hipStream_t st, const SplitClaim *cl)
 {
-    CtrParams P = ctr_params(in, out, nbytes, c, wrap64);
-    P.shift = c.lo & (CTR_BULK_PER - 1);
-    P.cbase.lo = c.lo - P.shift;
-    P.cl = cl;
-    const dim3 g(cl.wgs ? cl.wgs : (unsigned)num_cus()), b(1024);
-    switch (K.nr) {
-    case 10: hipLaunchKernelGGL(k_aes_ctr_tt_persist<10>, g, b, 0, st, P, K); break;
-    case 12: hipLaunchKernelGGL(k_aes_ctr_tt_persist<12>, g, b, 0, st, P, K); break;
-    case 14: hipLaunchKernelGGL(k_aes_ctr_tt_persist<14>, g, b, 0, st, P, K); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_rounds(K.nr, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        if (cl) {
+            CtrParams P = ctr_params(in, out, nbytes, c, wrap64, CTR_BULK_PER);
+            P.cl = *cl;
+            hipLaunchKernelGGL(k_aes_ctr_tt_persist<NR>, claim_grid(*cl), dim3(1024), 0, st, P, K);
+            return hipGetLastError();
+        }
+        /* one 1024- or 256-thread workgroup per CU (the 128 KiB 4-table image) */
+        return with_shape<1024, OTC_TT_CTR_B>(nbytes / 16 + (nbytes % 16 ? 1 : 0), [&](auto t, auto b) {
+            constexpr int T = decltype(t)::value, B = decltype(b)::value;
+            constexpr uint64_t PER = (uint64_t)T * B;
+            const CtrParams P = ctr_params(in, out, nbytes, c, wrap64, PER);
+            const uint64_t vt = P.nfull + (P.tail ? 1 : 0) + P.shift;
+            hipLaunchKernelGGL((k_aes_ctr_tt_cached<NR, B, T>), dim3(grid_for(vt, PER, 1)), dim3(T), 0, st, P, K);
+            return hipGetLastError();
+        });
+    });
 }
 
-template <bool CFB>
-static hipError_t chain_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                                    const otc_aes_key &K, Ctr128 iv0, hipStream_t st)
+hipError_t tt_seg_encrypt(bool cfb, const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
+                          const otc_aes_key &K, Ctr128 iv0, hipStream_t st, const SplitClaim *cl)
 {
     CbcSegParams P{};
     P.in = (const uint8_t *)in;
@@ -1550,18 +1478,11 @@ static hipError_t chain_encrypt_seg(const void *in, void *out, uint64_t seg_bloc
     P.seg_blocks = seg_blocks;
     P.nseg = nseg;
     P.iv0 = iv0;
-    switch (K.nr) {
-    case 10: return launch_seg_nr<10, CFB>(P, K, st);
-    case 12: return launch_seg_nr<12, CFB>(P, K, st);
-    case 14: return launch_seg_nr<14, CFB>(P, K, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t tt_cbc_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                              const otc_aes_key &K, Ctr128 iv0, hipStream_t st)
-{
-    return chain_encrypt_seg<false>(in, out, seg_blocks, nseg, K, iv0, st);
+    if (cl) P.cl = *cl;
+    return with_rounds(K.nr, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        return cfb ? launch_seg<NR, true>(P, K, cl != nullptr, st) : launch_seg<NR, false>(P, K, cl != nullptr, st);
+    });
 }
 
 hipError_t tt_ctr_shift(const void *body_in, void *body_out, size_t len, const otc_aes_key &K, Ctr128 c,
@@ -1579,13 +1500,10 @@ hipError_t tt_ctr_shift(const void *body_in, void *body_out, size_t len, const o
     constexpr int T = 1024;
     const uint64_t waves = ((a + len + 15) / 16 + 62) / 63;
     const int grid = grid_for(waves, T / 64, 1);
-    switch (K.nr) {
-    case 10: hipLaunchKernelGGL((k_aes_ctr_shift<10, T>), dim3(grid), dim3(T), 0, st, P, K); break;
-    case 12: hipLaunchKernelGGL((k_aes_ctr_shift<12, T>), dim3(grid), dim3(T), 0, st, P, K); break;
-    case 14: hipLaunchKernelGGL((k_aes_ctr_shift<14, T>), dim3(grid), dim3(T), 0, st, P, K); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_rounds(K.nr, [&](auto nr) {
+        hipLaunchKernelGGL((k_aes_ctr_shift<decltype(nr)::value, T>), dim3(grid), dim3(T), 0, st, P, K);
+        return hipGetLastError();
+    });
 }
 
 hipError_t xor_small(const void *in, void *out, uint32_t n, const uint8_t *ks, hipStream_t st)
@@ -1596,39 +1514,6 @@ hipError_t xor_small(const void *in, void *out, uint32_t n, const uint8_t *ks, h
     for (uint32_t i = 0; i < n; ++i) k.ks[i] = ks[i];
     hipLaunchKernelGGL(k_xor_small, dim3(1), dim3(64), 0, st, (const uint8_t *)in, (uint8_t *)out, n, k);
     return hipGetLastError();
-}
-
-hipError_t tt_cfb_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                              const otc_aes_key &K, Ctr128 iv0, hipStream_t st)
-{
-    return chain_encrypt_seg<true>(in, out, seg_blocks, nseg, K, iv0, st);
-}
-
-/* the T-table half of the chained segment-encryption split: 64-segment
- * units from the back of `cl` (cl.wgs workgroups, default one per CU) */
-hipError_t tt_seg_encrypt_claim(bool cfb, const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                                const otc_aes_key &K, Ctr128 iv0, SplitClaim cl, hipStream_t st)
-{
-    CbcSegParams P{};
-    P.in = (const uint8_t *)in;
-    P.out = (uint8_t *)out;
-    P.seg_blocks = seg_blocks;
-    P.nseg = nseg;
-    P.iv0 = iv0;
-    P.cl = cl;
-    const dim3 g(cl.wgs ? cl.wgs : (unsigned)num_cus()), b(1024);
-    constexpr int G = SEG_CLAIM_G;
-    auto go = [&](auto nr) {
-        constexpr int NR = decltype(nr)::value;
-        return cfb ? launch_dyn<k_aes_seg_enc_tt_claim<NR, G, true>>(g, b, ENC_LDS, st, P, K)
-                   : launch_dyn<k_aes_seg_enc_tt_claim<NR, G, false>>(g, b, ENC_LDS, st, P, K);
-    };
-    switch (K.nr) {
-    case 10: return go(std::integral_constant<int, 10>{});
-    case 12: return go(std::integral_constant<int, 12>{});
-    case 14: return go(std::integral_constant<int, 14>{});
-    default: return hipErrorInvalidValue;
-    }
 }
 
 } // namespace otc_impl

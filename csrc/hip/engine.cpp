@@ -117,9 +117,7 @@ hipError_t seg_enc_run(bool cfb, const void *in, void *out, size_t seg_bytes, si
     const size_t seg_blocks = seg_bytes / 16;
     g_last_impl = OTC_IMPL_TTABLE;
     auto launch = [&](const SplitClaim *cl) {
-        if (cl) return otc_impl::tt_seg_encrypt_claim(cfb, in, out, seg_blocks, nseg, K, iv0, *cl, st);
-        return cfb ? otc_impl::tt_cfb_encrypt_seg(in, out, seg_blocks, nseg, K, iv0, st)
-                   : otc_impl::tt_cbc_encrypt_seg(in, out, seg_blocks, nseg, K, iv0, st);
+        return otc_impl::tt_seg_encrypt(cfb, in, out, seg_blocks, nseg, K, iv0, st, cl);
     };
     if (!segenc_persistent(seg_bytes * nseg, nseg)) return launch(nullptr);
     return claim_alone(nseg / otc_dev::SEG_UNIT, 16, st, launch);
@@ -217,8 +215,7 @@ static int ctr_common(const void *in, void *out, size_t nbytes, const otc_aes_ke
         /* the T-table as a persistent claim kernel (first units handed out,
          * the rest claimed): no CU waits on another's static share */
         e = claim_alone(otc_impl::tt_ctr_claim_units(nbytes, c.lo), 2, st, [&](const SplitClaim *cl) {
-            return cl ? otc_impl::tt_ctr_claim(in, out, nbytes, *k, c, wrap64, *cl, st)
-                      : otc_impl::tt_ctr(in, out, nbytes, *k, c, wrap64, st);
+            return otc_impl::tt_ctr(in, out, nbytes, *k, c, wrap64, st, cl);
         });
     } else {
         e = otc_impl::tt_ctr(in, out, nbytes, *k, c, wrap64, st);

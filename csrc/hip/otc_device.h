@@ -161,22 +161,36 @@ struct SplitClaim {
  * from being cached, and the hint cut the headline kernel's J/GB by 2-3% and
  * raised its rate 1.7-1.8% under the power cap (round 6,
  * profiles/r6/nt_ab/).  The builtins take native vector types, not HIP's
- * uint4 struct. */
+ * uint4 struct.
+ * GLOBAL: p is a plain address that reached the kernel through memory (a
+ * descriptor), not an argument: access it as GLOBAL memory, or hipcc emits
+ * flat_* ops, which count against lgkmcnt and make every LDS wait also wait
+ * for HBM. */
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-template <bool NT>
+typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+template <bool NT, bool GLOBAL = false>
 __device__ __forceinline__ uint4 ld_u4(const void *p)
 {
-    if constexpr (NT) {
+    if constexpr (GLOBAL) {
+        const g_u32x4 *q = (const g_u32x4 *)p;
+        const u32x4 v = NT ? __builtin_nontemporal_load(q) : *q;
+        return make_uint4(v.x, v.y, v.z, v.w);
+    } else if constexpr (NT) {
         const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
         return make_uint4(v.x, v.y, v.z, v.w);
     } else {
         return *(const uint4 *)p;
     }
 }
-template <bool NT>
+template <bool NT, bool GLOBAL = false>
 __device__ __forceinline__ void st_u4(void *p, uint4 v)
 {
-    if constexpr (NT) {
+    if constexpr (GLOBAL) {
+        const u32x4 w = {v.x, v.y, v.z, v.w};
+        g_u32x4 *q = (g_u32x4 *)p;
+        if (NT) __builtin_nontemporal_store(w, q);
+        else *q = w;
+    } else if constexpr (NT) {
         const u32x4 w = {v.x, v.y, v.z, v.w};
         __builtin_nontemporal_store(w, (u32x4 *)p);
     } else {

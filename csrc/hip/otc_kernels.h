@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "otc.h"
 #include "otc_device.h"
 
@@ -40,7 +42,22 @@ inline int seg_shift_of(uint64_t seg_blocks)
     return seg_blocks && !(seg_blocks & (seg_blocks - 1)) ? __builtin_ctzll(seg_blocks) : -1;
 }
 
+/* The kernels take the round count as a template argument: f(the constant
+ * 10, 12 or 14 as a std::integral_constant) for a key's nr */
+template <class F>
+hipError_t with_rounds(int nr, F f)
+{
+    switch (nr) {
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 14: return f(std::integral_constant<int, 14>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
 /* ---- aes_tt.hip ---------------------------------------------------------- */
+/* `cl` of tt_ctr, tt_seg_encrypt and tt_ctr_batch: null for the grid kernel,
+ * else the persistent claim kernel over cl's units (claim_alone) */
 /* the grid T-table kernel over the first nblocks blocks of the job (segment
  * modes: rounded up to whole segments) */
 hipError_t tt_run(const Job &j, uint64_t nblocks, hipStream_t st);
@@ -48,19 +65,14 @@ hipError_t tt_run(const Job &j, uint64_t nblocks, hipStream_t st);
  * plus the blocks past its last unit (power-of-two segments only) */
 hipError_t tt_claim(const Job &j, SplitClaim cl, hipStream_t st);
 hipError_t tt_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
-                  hipStream_t st);
+                  hipStream_t st, const SplitClaim *cl = nullptr);
 uint64_t tt_ctr_claim_units(size_t nbytes, uint64_t ctr_lo);
-hipError_t tt_ctr_claim(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
-                        SplitClaim cl, hipStream_t st);
 hipError_t tt_ctr_shift(const void *body_in, void *body_out, size_t len, const otc_aes_key &K, Ctr128 c,
                         hipStream_t st);
 hipError_t xor_small(const void *in, void *out, uint32_t n, const uint8_t *ks, hipStream_t st);
-hipError_t tt_cbc_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg, const otc_aes_key &K,
-                              Ctr128 iv0, hipStream_t st);
-hipError_t tt_cfb_encrypt_seg(const void *in, void *out, uint64_t seg_blocks, uint64_t nseg, const otc_aes_key &K,
-                              Ctr128 iv0, hipStream_t st);
-hipError_t tt_seg_encrypt_claim(bool cfb, const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
-                                const otc_aes_key &K, Ctr128 iv0, SplitClaim cl, hipStream_t st);
+/* CBC (cfb false) or CFB128 encryption of nseg segments; cl: 64-segment units */
+hipError_t tt_seg_encrypt(bool cfb, const void *in, void *out, uint64_t seg_blocks, uint64_t nseg,
+                          const otc_aes_key &K, Ctr128 iv0, hipStream_t st, const SplitClaim *cl);
 /* cl null: the static split over the waves; else claimed runs of BATCH_UNIT tiles */
 hipError_t tt_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const uint32_t *tile_msg,
                         const uint64_t *tile_first, uint64_t ntiles, int tile_blocks, int nr, hipStream_t st,
