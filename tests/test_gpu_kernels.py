@@ -25,6 +25,42 @@ def host(t):
     return t.cpu().numpy().tobytes()
 
 
+UNIT = 2048 * 16  # bytes of one claim unit (otc_device.h CLAIM_UNIT blocks)
+
+
+def claimed_split(cus=None):
+    """(bytes, pf) of the smallest impl="split" shape whose pre-assigned front
+    (pf = 4 units per CU, the bitsliced waves'), claimed middle (2 per CU + 5)
+    and pre-assigned back (16 per CU, the T-table waves') are all non-empty
+    (split.cpp split_run), and 3 blocks past the last unit: about 176 MiB on
+    256 CUs.  Below 16 units per CU a split is the degenerate one -- every
+    unit pre-assigned to the T-table, the bitsliced kernel launched without
+    work (tests/test_gpu_split_coverage.py)."""
+    from our_tree_amd import _native
+
+    cus = cus or _native.require_gpu_lib().otc_device_cus(0)
+    return (22 * cus + 5) * UNIT + 48, 4 * cus
+
+
+def split_units(run):
+    """run() under otc_split_stats(1): (result, front, back, nunits) of the
+    claimed call it made (the stats mode waits for the call's kernels)."""
+    import ctypes
+
+    from our_tree_amd import _native
+
+    lib = _native.require_gpu_lib()
+    fr, bk, nu = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    lib.otc_split_stats(1)
+    try:
+        y = run()
+        torch.cuda.synchronize()
+        assert lib.otc_split_last_units(ctypes.byref(fr), ctypes.byref(bk), ctypes.byref(nu)) == 0
+    finally:
+        lib.otc_split_stats(0)
+    return y, fr.value, bk.value, nu.value
+
+
 @pytest.mark.parametrize("impl", IMPLS)
 @pytest.mark.parametrize("bits", KEYBITS)
 @pytest.mark.parametrize("n", [16, 1000, 4096 * 16 + 5, (1 << 20) + 3, 3 * (1 << 20) + 16 * 777])
@@ -458,12 +494,16 @@ def test_auto_routing_rule(gpu):
 
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_ecb_split_matches_ttable(gpu, bits):
-    """The co-resident split (T-table kernel on the caller's stream, bitsliced
-    kernel on the auxiliary stream, both taking 2048-block units of the whole
-    buffer from a shared counter) is byte-identical to the T-table alone, out
-    of place and in place: two units exactly, units plus a partial remainder
+    """An impl="split" call is byte-identical to the T-table alone, out of
+    place and in place: two units exactly, units plus a partial remainder
     (run by the T-table's workgroup 0), and a bulk size; under two units the
-    T-table runs alone."""
+    T-table runs alone.  Since the first units are handed out by the host
+    (split.cpp split_run) the shapes under 16 units per CU are the degenerate
+    split: every unit pre-assigned to the T-table waves, the bitsliced kernel
+    launched without work.  At 160 MiB on 256 CUs the bitsliced waves do run
+    their pre-assigned units (pf = 4 per CU) but nothing goes through the claim
+    word.  Both halves working over a claimed middle:
+    tests/test_gpu_split_coverage.py."""
     for n, want in ((64 * 2048 * 16 * 3 + 48, "split"), (2048 * 16 + 16, "ttable"), (160 << 20, "split"),
                     (2 * 2048 * 16, "split"), (2 * 2048 * 16 + 2047 * 16, "split")):
         key = os.urandom(bits // 8)
@@ -660,19 +700,27 @@ def test_persistent_ttable_midsize(gpu):
         del y, b
 
 
-def test_split_after_release_resources(gpu):
+@pytest.mark.parametrize("shape", ["small", "claimed"])
+def test_split_after_release_resources(gpu, shape):
     """otc_release_resources destroys the pooled split streams (both halves'
     CU-masked streams and their events); the next split builds them afresh
-    and still equals the T-table."""
+    and still equals the T-table.  small (1.25 MiB): the degenerate split,
+    every unit pre-assigned to the T-table waves, so the rebuilt bitsliced
+    stream carries a kernel without work.  claimed (claimed_split): the
+    rebuilt bitsliced stream does work -- front >= pf in both iterations."""
     from our_tree_amd import _native
 
     key = os.urandom(32)
-    n = 16 * 2048 * 40 + 48
+    n, pf = (16 * 2048 * 40 + 48, 0) if shape == "small" else claimed_split()
     x = torch.empty(n, dtype=torch.uint8, device=gpu)
     ops.fill_random_(x, seed=3)
     t = ops.ecb_encrypt(x, key, impl="ttable")
     for _ in range(2):
-        y = ops.ecb_encrypt(x, key, impl="split")
+        if pf:
+            y, front, back, nunits = split_units(lambda: ops.ecb_encrypt(x, key, impl="split"))
+            assert nunits == n // UNIT and front + back == nunits and front >= pf > 0, (front, back, nunits, pf)
+        else:
+            y = ops.ecb_encrypt(x, key, impl="split")
         assert ops.last_impl() == "split"
         torch.cuda.synchronize()
         assert torch.equal(y, t)
@@ -696,11 +744,17 @@ def test_ecb_split_stream_order(gpu):
     assert host(z[n - 4096:]) == exp
 
 
-def test_split_concurrent_calls(gpu):
+@pytest.mark.parametrize("shape", ["small", "claimed"])
+def test_split_concurrent_calls(gpu, shape):
     """Two splits in flight at once on two streams (each call has its own
     work counter and takes its own auxiliary stream from the pool), with ECB
-    encryption, ECB / CBC / CFB decryption, equal to the T-table."""
-    n = (96 << 20) + 4096 + 32
+    encryption, ECB / CBC / CFB decryption, equal to the T-table, and an ECB
+    pair in place.  small (96 MiB): under 16 units per CU, so two degenerate
+    splits -- every unit pre-assigned to the T-table waves, two bitsliced
+    kernels without work, two claim words no claim succeeds on.  claimed
+    (claimed_split): two bitsliced halves with work and two claim words in use
+    at once.  (No otc_split_stats here: that mode waits for each call.)"""
+    n = (96 << 20) + 4096 + 32 if shape == "small" else claimed_split()[0]
     key, iv = os.urandom(32), os.urandom(16)
     xs = [torch.empty(n, dtype=torch.uint8, device=gpu) for _ in range(2)]
     for i, x in enumerate(xs):
@@ -716,9 +770,22 @@ def test_split_concurrent_calls(gpu):
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 outs.append(f(x, "split"))
+                assert ops.last_impl() == "split", ops.split_fallback_reason()
         torch.cuda.synchronize()
         for x, y in zip(xs, outs):
             assert torch.equal(y, f(x, "ttable"))
+    del outs
+    # in place: a unit enciphered twice (by both halves, or by both calls' waves) shows
+    ws = [x.clone() for x in xs]
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream() for _ in ws]
+    for w, st in zip(ws, streams):
+        with torch.cuda.stream(st):
+            ops.ecb_encrypt(w, key, out=w, impl="split")
+            assert ops.last_impl() == "split", ops.split_fallback_reason()
+    torch.cuda.synchronize()
+    for x, w in zip(xs, ws):
+        assert torch.equal(w, ops.ecb_encrypt(x, key, impl="ttable"))
 
 
 @pytest.mark.parametrize("bits,n,want", [(128, (2 << 30) + 3, "bitslice"), (192, (2 << 30) + 3, "bitslice"),
@@ -751,8 +818,12 @@ def test_bitsliced_decrypt_matches_ttable(gpu, bits):
     """The bitsliced inverse cipher (the forward 77-LUT S-box as S^-1 = L S L,
     L o InvMixColumns o L between rounds, otc_invmix.h) and the decrypt split
     equal the T-table decryption, ECB (in and out of place) and CBC (IV on
-    block 0; the split's bitsliced part takes block nt-1 as its predecessor),
-    on sizes with partial first / last bitsliced tasks."""
+    block 0), on sizes with partial first / last bitsliced tasks.  The
+    bitsliced inverse cipher runs in the "bitslice" arm only: every size here
+    is under 16 units per CU, so the "split" arm is the degenerate split --
+    every unit pre-assigned to the T-table waves, the bitsliced kernel
+    launched without work.  Bitsliced decryption inside a split with a
+    claimed middle: tests/test_gpu_split_coverage.py."""
     for n in (16 * 2048 * 9 + 16 * 77, 16 * 100, 16 * 2048 * 40 + 16, 96 << 20):
         key = os.urandom(bits // 8)
         iv = os.urandom(16)
@@ -781,10 +852,13 @@ def test_bitsliced_decrypt_matches_ttable(gpu, bits):
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_bitsliced_cfb_decrypt_matches_ttable(gpu, bits):
     """Bitsliced CFB128 decryption (the forward cipher on the input shifted one
-    block back, the IV in front of block 0) and the CFB split (its bitsliced
-    part enciphers block nt-1 of the input) equal the T-table kernel and the
-    CPU oracle, on sizes with partial first / last bitsliced tasks, a single
-    block and a size that splits."""
+    block back, the IV in front of block 0) and the CFB split equal the
+    T-table kernel and the CPU oracle, on sizes with partial first / last
+    bitsliced tasks, a single block and a size that splits.  The bitsliced
+    kernel does work in the "bitslice" arm only: every size here is under 16
+    units per CU, so the "split" arm is the degenerate split -- every unit
+    pre-assigned to the T-table waves.  The bitsliced part of a CFB split at
+    work: tests/test_gpu_split_coverage.py."""
     for n in (16, 16 * 2048 * 9 + 16 * 77, 16 * 100, 16 * 2048 * 40 + 16, 96 << 20):
         key = os.urandom(bits // 8)
         iv = os.urandom(16)
@@ -813,7 +887,12 @@ def test_segment_decrypt_split_matches_ttable(gpu, bits):
     carry across the low 64 bits of the IV included) through the claimed
     split equals the T-table kernel and the CPU oracle, for segments of 1, 32,
     256 and 4096 blocks, with a partial last unit; a non-power-of-two segment
-    size runs the T-table."""
+    size runs the T-table.  At 1.25 MiB this is the degenerate split: every
+    unit pre-assigned to the T-table waves, the bitsliced segment kernels
+    launched without work -- the routing and the T-table claim kernel's segment
+    forms are what it checks.  The bitsliced segment kernels at these segment
+    sizes, alone and inside a split with a claimed middle:
+    tests/test_gpu_split_coverage.py."""
     key = os.urandom(bits // 8)
     iv0 = os.urandom(8) + (2**64 - 3).to_bytes(8, "big")
     for seg in (16, 512, 4096, 65536):

@@ -159,7 +159,10 @@ def test_split_halves_coresident_in_busy_process(gpu, rccl_world1, busy_streams,
 
 def test_split_fallback_reason(gpu):
     """A split request that cannot split runs the T-table and says why
-    (otc_split_fallback_reason); one that splits leaves it empty."""
+    (otc_split_fallback_reason); one that splits leaves it empty.  The 2 MiB
+    call is the degenerate split -- every unit pre-assigned to the T-table
+    waves, the bitsliced kernel launched without work; the reason is empty
+    with both halves at work too (tests/test_gpu_split_coverage.py)."""
     from our_tree_amd import ops
 
     key = bytes(range(32))
@@ -183,32 +186,49 @@ def host_bytes(t):
     return t.cpu().numpy().tobytes()
 
 
-def test_split_captured_in_graph(gpu):
+@pytest.mark.parametrize("shape", ["small", "claimed"])
+def test_split_captured_in_graph(gpu, shape):
     """A split call captured into a HIP graph (torch.cuda.CUDAGraph: stream
     capture of the fork / join events, the claim counter's stream-ordered
-    allocation and both halves' launches) replays to the right bytes; a call
-    made while capturing never synchronises (split.cpp aux_take: no warm-up
-    under capture)."""
-    from our_tree_amd import ops
+    allocation and reset, and both halves' launches) replays to the right
+    bytes, twice, the output zeroed before each replay; a call made while
+    capturing never synchronises (split.cpp aux_take: no warm-up under
+    capture).  small (2 MiB): the degenerate split, every unit pre-assigned to
+    the T-table waves -- no unit goes through the counter, so a replay without
+    the captured reset would still be right.  claimed: 4 units per CU
+    pre-assigned to the bitsliced waves, 2 per CU + 5 through the claim word,
+    16 per CU to the T-table waves (split.cpp split_run; about 176 MiB on 256
+    CUs, see tests/test_gpu_split_coverage.py).  The graph holds the call
+    twice: the second call's counter is allocated behind the first one's
+    free, and a counter that is not reset claims nothing and leaves the middle
+    of the output zero."""
+    from our_tree_amd import _native, ops
 
     key = bytes(range(32))
-    x = torch.empty(64 * 2048 * 16, dtype=torch.uint8, device=gpu)
+    n = 64 * 2048 * 16
+    if shape == "claimed":
+        n = (22 * _native.require_gpu_lib().otc_device_cus(0) + 5) * 2048 * 16 + 48
+    x = torch.empty(n, dtype=torch.uint8, device=gpu)
     ops.fill_random_(x, seed=8)
-    o = torch.empty_like(x)
-    ops.ecb_encrypt(x, key, out=o, impl="split")
+    ref = cpu_ref.ecb(key, host_bytes(x), threads=8)
+    outs = [torch.empty_like(x) for _ in range(2)]
+    ops.ecb_encrypt(x, key, out=outs[0], impl="split")
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
+    ran = []
     with torch.cuda.graph(g):
-        ops.ecb_encrypt(x, key, out=o, impl="split")
-        ran = ops.last_impl()
-    assert ran == "split", (ran, ops.split_fallback_reason())
-    o.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    assert host_bytes(o) == cpu_ref.ecb(key, host_bytes(x))
-    g.replay()
-    torch.cuda.synchronize()
-    assert host_bytes(o) == cpu_ref.ecb(key, host_bytes(x))
+        for o in outs:
+            ops.ecb_encrypt(x, key, out=o, impl="split")
+            ran.append((ops.last_impl(), ops.split_fallback_reason()))
+    assert ran == [("split", "")] * 2, ran
+    for replay in (1, 2):
+        for o in outs:
+            o.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        for i, o in enumerate(outs):
+            same = host_bytes(o) == ref  # not inside the assert: no diff of the whole buffer in the report
+            assert same, f"replay {replay}, call {i}"
 
 
 @pytest.mark.parametrize("pooled", [False, True])
