@@ -4,7 +4,7 @@
  * per configuration.
  *
  *   otbench --mode ctr|ecb|ecb-dec|cbc-dec|cbc-enc-seg|cfb-enc-seg|cfb-dec-seg|cbc-dec-seg|cfb-dec|ctr-stream|xor|rc4
- *                  |ecb-split|ecbdec-split|cbcdec-split|cfbdec-split|ctr-split
+ *                  |ecb-split|ecbdec-split|cbcdec-split|cfbdec-split|ctr-split|xts-enc|xts-dec
  *           [--bits 128] [--bytes 1G] [--iters 20] [--warmup 3]
  *           [--impl auto|ttable|bitslice|split] [--inplace] [--verify] [--clock]
  *           [--mark]                        "OTB_MARK start|end" on stderr around the timed loop
@@ -16,6 +16,8 @@
  *           [--e2e --chunk 256M]            host-resident, pinned pipeline
  *           [--gpus N --strategy direct|rccl] single-process multi-GPU (e2e)
  *           [--seg 4096]                    CBC segment size
+ *           [--unit 4096]                   xts-enc / xts-dec: bytes per data unit (a multiple of 16);
+ *                                           --bits 128|256 is the size of each key half
  *           [--share 0.2]                   *-split: the bitsliced kernel's share of the
  *                                           blocks, run CONCURRENTLY with the T-table kernel
  *                                           on the rest (two streams, co-resident per CU) --
@@ -82,11 +84,14 @@ struct OpArg {
     Cfg *c;
     void *in, *out;
     otc_aes_key *k;
+    otc_xts_key *xk; /* xts-enc / xts-dec */
     uint8_t iv[16];
     uint8_t *keys;
     void *sa, *sb; /* *-split: T-table / bitsliced streams */
     uint8_t prev[16]; /* cbcdec-split / cfbdec-split: ciphertext block before the bitsliced part */
 };
+
+static bool is_xts(const std::string &m) { return m == "xts-enc" || m == "xts-dec"; }
 
 static bool is_split(const std::string &m)
 {
@@ -152,6 +157,8 @@ static int run_op(void *p)
     if (c.mode == "cbc-dec-seg")
         return otc_aes_cbc_decrypt_segments_impl(a->in, a->out, c.seg, c.bytes / c.seg, a->k, a->iv, c.impl, nullptr);
     if (c.mode == "cfb-dec") return otc_aes_cfb128_decrypt_impl(a->in, a->out, c.bytes, a->k, a->iv, c.impl, nullptr);
+    if (is_xts(c.mode)) /* --unit BYTES per data unit, tweak0 = iv as a little-endian number */
+        return otc_aes_xts(a->in, a->out, c.seg, c.bytes / c.seg, a->xk, a->iv, nullptr);
     if (c.mode == "xor") return otc_xor(a->in, a->out, a->out, c.bytes, nullptr);
     if (c.mode == "rc4") return otc_rc4_multi(a->keys, (int)c.keylen, c.streams, c.len, c.drop, a->in, a->out, nullptr);
     return OTC_ERR_ARG;
@@ -171,7 +178,8 @@ struct Sample {
 
 static bool is_seg_mode(const std::string &m)
 {
-    return m == "cbc-enc-seg" || m == "cfb-enc-seg" || m == "cfb-dec-seg" || m == "cbc-dec-seg";
+    /* XTS data units are sampled, and numbered, like segments */
+    return m == "cbc-enc-seg" || m == "cfb-enc-seg" || m == "cfb-dec-seg" || m == "cbc-dec-seg" || is_xts(m);
 }
 static bool chained_dec(const std::string &m)
 {
@@ -235,7 +243,7 @@ static bool snapshot(const Cfg &c, const OpArg &a, CopyFn cp, std::vector<Sample
 }
 
 /* the oracle's output for one sample; false if the mode has no oracle */
-static bool oracle(const Cfg &c, const uint8_t key[32], const uint8_t iv0[16], const Sample &s, std::vector<uint8_t> &ref)
+static bool oracle(const Cfg &c, const uint8_t key[64], const uint8_t iv0[16], const Sample &s, std::vector<uint8_t> &ref)
 {
     ref.assign(s.len, 0);
     const uint8_t *in = s.in.data() + s.pre;
@@ -277,6 +285,22 @@ static bool oracle(const Cfg &c, const uint8_t key[32], const uint8_t iv0[16], c
             int iv_off = 0;
             aes_crypt_cfb128(&ctx, AES_DECRYPT, s.len, &iv_off, iv, in, ref.data());
         }
+    } else if (is_xts(m)) {
+        /* unit q: tweak number iv0 + q, a 128-bit little-endian add */
+        aes_xts_context x;
+        if (m == "xts-dec")
+            aes_xts_setkey_dec(&x, key, 2 * c.bits);
+        else
+            aes_xts_setkey_enc(&x, key, 2 * c.bits);
+        uint8_t tw[16];
+        memcpy(tw, iv0, 16);
+        uint64_t carry = s.seg0;
+        for (int i = 0; i < 16 && carry; ++i) {
+            const uint64_t v = tw[i] + (carry & 0xFF);
+            tw[i] = (uint8_t)v;
+            carry = (carry >> 8) + (v >> 8);
+        }
+        aes_crypt_xts_units(&x, m == "xts-dec" ? AES_DECRYPT : AES_ENCRYPT, c.seg, s.len / c.seg, tw, in, ref.data());
     } else if (is_seg_mode(m)) {
         /* segment q: IV_q = iv0 + q (128-bit BE add), its own chain */
         if (m == "cbc-dec-seg")
@@ -312,7 +336,7 @@ static bool oracle(const Cfg &c, const uint8_t key[32], const uint8_t iv0[16], c
 
 /* 1: every sample matched, 0: a mismatch (message on stderr), -1: no oracle
  * or a copy failed (reported as not verified) */
-static int check_samples(const Cfg &c, const OpArg &a, CopyFn cp, const uint8_t key[32],
+static int check_samples(const Cfg &c, const OpArg &a, CopyFn cp, const uint8_t key[64],
                          const std::vector<Sample> &samples)
 {
     if (samples.empty()) return -1;
@@ -393,7 +417,7 @@ int main(int argc, char **argv)
         else if (a == "--chunk") c.chunk = parse_size(nx());
         else if (a == "--gpus") c.gpus = atoi(nx());
         else if (a == "--strategy") c.strategy = std::string(nx()) == "rccl" ? 1 : 0;
-        else if (a == "--seg") c.seg = parse_size(nx());
+        else if (a == "--seg" || a == "--unit") c.seg = parse_size(nx());
         else if (a == "--share") c.share = atof(nx());
         else if (a == "--streams") c.streams = parse_size(nx());
         else if (a == "--len") c.len = parse_size(nx());
@@ -407,7 +431,7 @@ int main(int argc, char **argv)
     static const char *modes[] = {"ctr", "ecb", "ecb-dec", "cbc-dec", "cbc-enc-seg", "cfb-enc-seg", "cfb-dec-seg",
                                   "cbc-dec-seg",
                                   "cfb-dec", "ctr-stream", "xor", "rc4", "ecb-split", "ecbdec-split", "cbcdec-split",
-                                  "cfbdec-split", "ctr-split"};
+                                  "cfbdec-split", "ctr-split", "xts-enc", "xts-dec"};
     bool known = false;
     for (const char *m : modes) known |= c.mode == m;
     if (!known) {
@@ -418,7 +442,11 @@ int main(int argc, char **argv)
     if (c.mode != "ctr" && c.mode != "ctr-stream" && c.mode != "xor" && c.mode != "rc4") c.bytes &= ~(size_t)15;
     if (is_seg_mode(c.mode)) {
         if (c.seg == 0 || c.seg % 16) {
-            fprintf(stderr, "--seg must be a positive multiple of 16\n");
+            fprintf(stderr, "--seg / --unit must be a positive multiple of 16\n");
+            return 2;
+        }
+        if (is_xts(c.mode) && (c.seg > (16u << 20) || (c.bits != 128 && c.bits != 256))) {
+            fprintf(stderr, "xts: --unit is at most 16M (2^20 blocks), --bits 128 or 256\n");
             return 2;
         }
         c.bytes = (c.bytes / c.seg) * c.seg;
@@ -437,9 +465,9 @@ int main(int argc, char **argv)
         return 2;
     }
 
-    uint8_t key[32];
+    uint8_t key[64]; /* AES: the first bits / 8 bytes; XTS: K1 || K2, the first bits / 4 */
     srand(1337);
-    for (int i = 0; i < 32; ++i) key[i] = (uint8_t)rand();
+    for (int i = 0; i < 64; ++i) key[i] = (uint8_t)rand();
     const bool dec = (c.mode == "ecb-dec" || c.mode == "cbc-dec" || c.mode == "ecbdec-split" ||
                       c.mode == "cbcdec-split" || c.mode == "cbc-dec-seg");
     otc_aes_key k;
@@ -447,9 +475,15 @@ int main(int argc, char **argv)
         fprintf(stderr, "key: %s\n", otc_last_error());
         return 1;
     }
+    otc_xts_key xk;
+    if (is_xts(c.mode) && otc_xts_key_init(&xk, key, 2 * c.bits, c.mode == "xts-dec" ? OTC_DIR_DECRYPT : OTC_DIR_ENCRYPT)) {
+        fprintf(stderr, "key: %s\n", otc_last_error());
+        return 1;
+    }
     OpArg a{};
     a.c = &c;
     a.k = &k;
+    a.xk = &xk;
     for (int i = 0; i < 16; ++i) a.iv[i] = (uint8_t)(0xF0 + i);
 
     const int cus = otc_device_cus(0);

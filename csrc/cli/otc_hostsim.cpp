@@ -205,6 +205,27 @@ int otc_aes_cfb128_decrypt(const void *in, void *out, size_t n, const otc_aes_ke
     return aes_crypt_cfb128(&c, AES_DECRYPT, n, &iv_off, v, (const uint8_t *)in, (uint8_t *)out);
 }
 
+int otc_xts_key_init(otc_xts_key *k, const uint8_t *key, int keybits, int dir)
+{
+    if (keybits != 256 && keybits != 512) return fail(OTC_ERR_ARG, "invalid XTS key size");
+    if (int r = otc_aes_key_init(&k->data, key, keybits / 2, dir)) return r;
+    return otc_aes_key_init(&k->tweak, key + keybits / 16, keybits / 2, OTC_DIR_ENCRYPT);
+}
+
+int otc_aes_xts(const void *in, void *out, size_t unit, size_t nunits, const otc_xts_key *k, const uint8_t tweak0[16],
+                void *)
+{
+    if (unit < 16 || unit > ((size_t)16 << 20) || (nunits > 1 && unit % 16)) return fail(OTC_ERR_ARG, "xts unit");
+    if (nunits == 0) return OTC_OK;
+    aes_xts_context c;
+    aes_import_rk32(&c.crypt, k->data.rk, k->data.nr);
+    aes_import_rk32(&c.tweak, k->tweak.rk, k->tweak.nr);
+    return aes_crypt_xts_units(&c, k->data.dir == OTC_DIR_ENCRYPT ? AES_ENCRYPT : AES_DECRYPT, unit, nunits, tweak0,
+                               (const uint8_t *)in, (uint8_t *)out)
+               ? fail(OTC_ERR_ARG, "xts length")
+               : OTC_OK;
+}
+
 int otc_xor(const void *a, const void *b, void *out, size_t n, void *)
 {
     for (size_t i = 0; i < n; ++i) ((uint8_t *)out)[i] = ((const uint8_t *)a)[i] ^ ((const uint8_t *)b)[i];

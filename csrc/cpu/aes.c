@@ -414,6 +414,135 @@ int aes_ecb_bulk(const aes_context *ctx, int mode, const unsigned char *input,
 }
 
 /* ---------------------------------------------------------------------------
+ * XTS-AES (IEEE 1619 / SP 800-38E), written from the standard's definition:
+ * T_0 = E_K2(data unit number as a 128-bit little-endian block), T_{j+1} =
+ * T_j * alpha in GF(2^128) (x^128 + x^7 + x^2 + x + 1, T read as a
+ * little-endian integer), C_j = E_K1(P_j ^ T_j) ^ T_j, ciphertext stealing
+ * for a last block of 1..15 bytes.  In place (input == output) is exact:
+ * every block is read before it is written.
+ * ------------------------------------------------------------------------- */
+int aes_xts_setkey_enc(aes_xts_context *ctx, const unsigned char *key, unsigned int keybits)
+{
+    if (keybits != 256 && keybits != 512) return POLARSSL_ERR_AES_INVALID_KEY_LENGTH;
+    int r = aes_setkey_enc(&ctx->crypt, key, keybits / 2);
+    return r ? r : aes_setkey_enc(&ctx->tweak, key + keybits / 16, keybits / 2);
+}
+
+int aes_xts_setkey_dec(aes_xts_context *ctx, const unsigned char *key, unsigned int keybits)
+{
+    if (keybits != 256 && keybits != 512) return POLARSSL_ERR_AES_INVALID_KEY_LENGTH;
+    int r = aes_setkey_dec(&ctx->crypt, key, keybits / 2);
+    return r ? r : aes_setkey_enc(&ctx->tweak, key + keybits / 16, keybits / 2); /* always encrypts */
+}
+
+/* T *= alpha: shift the little-endian integer left one bit, fold the carry */
+static void xts_mul_alpha(unsigned char t[16])
+{
+    unsigned carry = 0;
+    for (int i = 0; i < 16; ++i) {
+        const unsigned v = ((unsigned)t[i] << 1) | carry;
+        carry = t[i] >> 7;
+        t[i] = (unsigned char)v;
+    }
+    if (carry) t[0] ^= 0x87;
+}
+
+static void xts_block(const aes_context *k1, int mode, const unsigned char t[16], const unsigned char in[16],
+                      unsigned char out[16])
+{
+    unsigned char x[16];
+    for (int i = 0; i < 16; ++i) x[i] = (unsigned char)(in[i] ^ t[i]);
+    if (mode == AES_ENCRYPT)
+        encrypt_block(k1, x, x);
+    else
+        decrypt_block(k1, x, x);
+    for (int i = 0; i < 16; ++i) out[i] = (unsigned char)(x[i] ^ t[i]);
+}
+
+int aes_crypt_xts(aes_xts_context *ctx, int mode, size_t length, const unsigned char data_unit[16],
+                  const unsigned char *input, unsigned char *output)
+{
+    if (length < 16 || length > ((size_t)1 << 24)) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    const size_t m = length / 16, r = length % 16;
+    unsigned char t[16];
+    encrypt_block(&ctx->tweak, data_unit, t);
+    const size_t plain = r ? m - 1 : m; /* blocks before the stolen pair */
+    for (size_t j = 0; j < plain; ++j) {
+        xts_block(&ctx->crypt, mode, t, input + 16 * j, output + 16 * j);
+        xts_mul_alpha(t);
+    }
+    if (r) {
+        /* t = T_{m-1}, t1 = T_m; decryption uses them in the other order */
+        unsigned char t1[16], cc[16], last[16];
+        memcpy(t1, t, 16);
+        xts_mul_alpha(t1);
+        const unsigned char *in_full = input + 16 * (m - 1), *in_part = input + 16 * m;
+        xts_block(&ctx->crypt, mode, mode == AES_ENCRYPT ? t : t1, in_full, cc);
+        memcpy(last, in_part, r);
+        memcpy(last + r, cc + r, 16 - r);
+        xts_block(&ctx->crypt, mode, mode == AES_ENCRYPT ? t1 : t, last, last);
+        memcpy(output + 16 * m, cc, r);
+        memcpy(output + 16 * (m - 1), last, 16);
+    }
+    return 0;
+}
+
+/* tweak number + n as a 128-bit little-endian integer (wraps at 2^128) */
+static void xts_tweak_add(unsigned char t[16], uint64_t n)
+{
+    uint64_t carry = n;
+    for (int i = 0; i < 16 && carry; ++i) {
+        const uint64_t v = (uint64_t)t[i] + (carry & 0xff);
+        t[i] = (unsigned char)v;
+        carry = (carry >> 8) + (v >> 8);
+    }
+}
+
+typedef struct {
+    aes_xts_context *ctx;
+    int mode;
+    size_t unit_bytes, first, count;
+    const unsigned char *tweak0, *in;
+    unsigned char *out;
+} xts_job;
+
+static void *xts_worker(void *arg)
+{
+    xts_job *j = (xts_job *)arg;
+    for (size_t u = j->first; u < j->first + j->count; ++u) {
+        unsigned char du[16];
+        memcpy(du, j->tweak0, 16);
+        xts_tweak_add(du, (uint64_t)u);
+        aes_crypt_xts(j->ctx, j->mode, j->unit_bytes, du, j->in + u * j->unit_bytes, j->out + u * j->unit_bytes);
+    }
+    return NULL;
+}
+
+int aes_crypt_xts_units(aes_xts_context *ctx, int mode, size_t unit_bytes, size_t nunits,
+                        const unsigned char tweak0[16], const unsigned char *input, unsigned char *output)
+{
+    if (unit_bytes < 16 || unit_bytes > ((size_t)1 << 24)) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    if (nunits > 1 && unit_bytes % 16) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    /* units are independent: large calls (the device tests' oracle) run on
+     * up to 8 threads */
+    enum { MAXT = 8 };
+    size_t nt = unit_bytes * nunits >= ((size_t)4 << 20) ? MAXT : 1;
+    if (nt > nunits) nt = nunits ? nunits : 1;
+    xts_job jobs[MAXT];
+    pthread_t th[MAXT];
+    size_t first = 0;
+    for (size_t t = 0; t < nt; ++t) {
+        const size_t count = nunits / nt + (t < nunits % nt ? 1 : 0);
+        jobs[t] = (xts_job){ctx, mode, unit_bytes, first, count, tweak0, input, output};
+        first += count;
+    }
+    for (size_t t = 1; t < nt; ++t) pthread_create(&th[t], NULL, xts_worker, &jobs[t]);
+    xts_worker(&jobs[0]);
+    for (size_t t = 1; t < nt; ++t) pthread_join(th[t], NULL);
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------
  * Self test: FIPS-197 appendix C, SP 800-38A F.1/F.2/F.3/F.5, RFC 3686 #1-#3,
  * and the 10,000-iteration Monte-Carlo ECB/CBC chains of the NIST
  * rijndael-vals set that the reference's self-test runs

@@ -500,6 +500,46 @@ extern "C" int otc_aes_cfb128_decrypt(const void *in, void *out, size_t nbytes, 
     return otc_aes_cfb128_decrypt_impl(in, out, nbytes, k, iv, OTC_IMPL_AUTO, stream);
 }
 
+/* ---- XTS ------------------------------------------------------------------ */
+extern "C" int otc_xts_key_init(otc_xts_key *k, const uint8_t *key, int keybits, int dir)
+{
+    if (!k || !key) return set_err(OTC_ERR_ARG, "null argument");
+    if (keybits != 256 && keybits != 512)
+        return set_err(OTC_ERR_ARG, "invalid XTS key size (K1 || K2 must be 256 or 512 bits)");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (int r = otc_aes_key_init(&k->data, key, keybits / 2, dir)) return r;
+    return otc_aes_key_init(&k->tweak, key + keybits / 16, keybits / 2, OTC_DIR_ENCRYPT);
+}
+
+extern "C" int otc_aes_xts(const void *in, void *out, size_t unit_bytes, size_t nunits, const otc_xts_key *k,
+                           const uint8_t tweak0[16], void *stream)
+{
+    Range rg("otc_aes_xts");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->tweak, OTC_DIR_ENCRYPT)) return r;
+    if ((k->data.nr != 10 && k->data.nr != 14) || k->data.nr != k->tweak.nr ||
+        (k->data.dir != OTC_DIR_ENCRYPT && k->data.dir != OTC_DIR_DECRYPT))
+        return set_err(OTC_ERR_ARG, "bad XTS key (two AES-128 or two AES-256 schedules)");
+    if (!tweak0) return set_err(OTC_ERR_ARG, "null tweak");
+    if (unit_bytes < 16) return set_err(OTC_ERR_ARG, "XTS data unit must be at least 16 bytes");
+    if (unit_bytes > ((size_t)16 << 20)) return set_err(OTC_ERR_ARG, "XTS data unit above 2^20 blocks");
+    if (nunits > 1 && unit_bytes % 16)
+        return set_err(OTC_ERR_ARG, "XTS data units of several must be multiples of 16 bytes");
+    if (nunits && unit_bytes > SIZE_MAX / nunits) return set_err(OTC_ERR_ARG, "size overflow");
+    if (int r = check_bufs(in, out, unit_bytes * nunits, true, "aes_xts")) return r;
+    if (nunits == 0) return OTC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    g_last_impl = OTC_IMPL_TTABLE;
+    const uint32_t m = (uint32_t)(unit_bytes / 16), r = (uint32_t)(unit_bytes % 16);
+    /* whole blocks: the bulk kernel; a stolen tail (one unit only): the bulk
+     * kernel up to block m - 2, then the last 16 + r bytes behind it */
+    const uint64_t nblocks = r ? m - 1u : (uint64_t)m * nunits;
+    hipError_t e = otc_impl::xts_bulk(in, out, nblocks, r ? (m > 1 ? m - 1u : 1u) : m, k->data, k->tweak, tweak0, st);
+    if (e == hipSuccess && r) e = otc_impl::xts_steal(in, out, m, r, k->data, k->tweak, tweak0, st);
+    if (e != hipSuccess) return hip_fail(e, "aes_xts launch");
+    return OTC_OK;
+}
+
 extern "C" int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream)
 {
     Range rg("otc_xor");

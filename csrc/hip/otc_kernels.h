@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_bs.hip, stream_ops.hip), declared once: included by their callers
+ * aes_xts.hip, aes_bs.hip, stream_ops.hip), declared once: included by their callers
  * (engine.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
  * of the public C API (otc.h).
@@ -79,6 +79,17 @@ hipError_t tt_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const 
                         const SplitClaim *cl);
 uint64_t tt_ctr_batch_units(uint64_t ntiles);
 int strace_read_tt(unsigned long long *buf, int max);
+
+/* ---- aes_xts.hip --------------------------------------------------------- */
+/* XTS over nblocks whole blocks in units of unit_blocks (1 .. 2^20); unit s
+ * uses tweak number tweak0 + s (128-bit little-endian).  K1: the data key in
+ * the call's direction, K2: the tweak key's encryption schedule. */
+hipError_t xts_bulk(const void *in, void *out, uint64_t nblocks, uint32_t unit_blocks, const otc_aes_key &K1,
+                    const otc_aes_key &K2, const uint8_t tweak0[16], hipStream_t st);
+/* ciphertext stealing: the last 16 + r bytes of ONE unit of 16 m + r bytes
+ * (queued behind xts_bulk over its first m - 1 blocks) */
+hipError_t xts_steal(const void *in, void *out, uint32_t m, uint32_t r, const otc_aes_key &K1, const otc_aes_key &K2,
+                     const uint8_t tweak0[16], hipStream_t st);
 
 /* ---- aes_bs.hip ---------------------------------------------------------- */
 hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,

@@ -74,6 +74,26 @@ int aes_ctr_bulk(const aes_context *ctx, const unsigned char nonce_counter[16],
 int aes_ecb_bulk(const aes_context *ctx, int mode, const unsigned char *input,
                  unsigned char *output, size_t length, int nthreads);
 
+/* XTS-AES (IEEE 1619 / SP 800-38E), shaped like the later PolarSSL / mbed TLS
+ * API (the reference's aes.c predates the mode; this is written from the
+ * standard).  The key is K1 || K2, 256 or 512 bits in all; `tweak` is always
+ * an encryption schedule.  Equal halves are accepted. */
+typedef struct {
+    aes_context crypt; /* K1, the direction of the setkey call */
+    aes_context tweak; /* K2 */
+} aes_xts_context;
+int aes_xts_setkey_enc(aes_xts_context *ctx, const unsigned char *key, unsigned int keybits);
+int aes_xts_setkey_dec(aes_xts_context *ctx, const unsigned char *key, unsigned int keybits);
+/* one data unit of 16 bytes .. 16 MiB (2^20 blocks); a length that is not a
+ * multiple of 16 uses ciphertext stealing.  data_unit: the 128-bit
+ * little-endian tweak number.  May run in place. */
+int aes_crypt_xts(aes_xts_context *ctx, int mode, size_t length, const unsigned char data_unit[16],
+                  const unsigned char *input, unsigned char *output);
+/* nunits consecutive units; unit s uses tweak0 + s (128-bit little-endian
+ * add, carry through all 16 bytes).  unit_bytes % 16 == 0 unless nunits == 1. */
+int aes_crypt_xts_units(aes_xts_context *ctx, int mode, size_t unit_bytes, size_t nunits,
+                        const unsigned char tweak0[16], const unsigned char *input, unsigned char *output);
+
 /* Monte-Carlo known-answer chains of the reference self-test
  * (aes-modes/aes.c:1084-1200): 10,000 chained operations from an all-zero
  * key / block / IV.  aes_monte_carlo writes the final block (CBC-enc: the last

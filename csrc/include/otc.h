@@ -189,6 +189,27 @@ int otc_aes_cfb128_decrypt_segments(const void *in, void *out, size_t seg_bytes,
 int otc_aes_cfb128_decrypt_segments_impl(const void *in, void *out, size_t seg_bytes, size_t nseg,
                                          const otc_aes_key *k, const uint8_t iv0[16], int impl, void *stream);
 
+/* XTS-AES (IEEE 1619 / SP 800-38E) over nunits data units (sectors) of
+ * unit_bytes each, fully parallel in both directions.  The key is K1 || K2:
+ * `data` is K1's schedule in the call's direction, `tweak` K2's -- always an
+ * encryption schedule.  Equal key halves are accepted: this is the primitive,
+ * and a policy such as SP 800-38E's K1 != K2 belongs to its caller.
+ * Unit s uses tweak number tweak0 + s, a 128-bit LITTLE-endian value (add
+ * with carry through all 16 bytes; dm-crypt plain64 is LE64(sector) || 0^8).
+ * unit_bytes is 16 .. 2^24 (2^20 blocks) and a multiple of 16 when nunits > 1;
+ * a single unit may have any length in that range and then ends with
+ * ciphertext stealing.  The direction comes from the key; in place is allowed
+ * both ways; buffers are 16-byte aligned as for otc_aes_ecb.  nunits == 0
+ * launches nothing.  Runs the grid T-table kernels of aes_xts.hip
+ * (otc_last_impl: OTC_IMPL_TTABLE), tuned for units up to 64 KiB. */
+typedef struct {
+    otc_aes_key data;
+    otc_aes_key tweak; /* always an encryption schedule */
+} otc_xts_key;
+int otc_xts_key_init(otc_xts_key *k, const uint8_t *key, int keybits /* 256 | 512 */, int dir);
+int otc_aes_xts(const void *in, void *out, size_t unit_bytes, size_t nunits, const otc_xts_key *k,
+                const uint8_t tweak0[16], void *stream);
+
 /* CFB128 decryption (parallel): P_i = C_i ^ E(C_{i-1}), C_{-1} = iv;
  * nbytes % 16 == 0; encryption key.  _impl: with a kernel choice (the plain
  * form is OTC_IMPL_AUTO: the T-table + bitsliced split from 2 GiB, the

@@ -60,6 +60,19 @@ class AesContext(ctypes.Structure):
     ]
 
 
+class AesXtsContext(ctypes.Structure):
+    """Mirror of ``aes_xts_context`` {crypt, tweak} (aes.h)."""
+
+    _fields_ = [("crypt", AesContext), ("tweak", AesContext)]
+
+
+class OtcXtsKey(ctypes.Structure):
+    """Mirror of ``otc_xts_key`` (otc.h): K1's schedule in the call's
+    direction and K2's encryption schedule."""
+
+    _fields_ = [("data", OtcAesKey), ("tweak", OtcAesKey)]
+
+
 class Arc4Context(ctypes.Structure):
     """Mirror of ``arc4_context`` {x, y, m[256]} (reference arc4.h:35-41)."""
 
@@ -130,6 +143,10 @@ def _declare_cpu(lib):
         "aes_ctr_bulk": (c_int, [P(AesContext), c_u8p, c_u8p, c_u8p, c_sz, c_int]),
         "aes_ecb_bulk": (c_int, [P(AesContext), c_int, c_u8p, c_u8p, c_sz, c_int]),
         "aes_ctr128_add": (None, [c_u8p, c_u64]),
+        "aes_xts_setkey_enc": (c_int, [P(AesXtsContext), c_u8p, ctypes.c_uint]),
+        "aes_xts_setkey_dec": (c_int, [P(AesXtsContext), c_u8p, ctypes.c_uint]),
+        "aes_crypt_xts": (c_int, [P(AesXtsContext), c_int, c_sz, c_u8p, c_u8p, c_u8p]),
+        "aes_crypt_xts_units": (c_int, [P(AesXtsContext), c_int, c_sz, c_sz, c_u8p, c_u8p, c_u8p]),
         "arc4_setup": (None, [P(Arc4Context), c_u8p, ctypes.c_uint]),
         "arc4_prep": (c_int, [P(Arc4Context), c_sz, c_u8p]),
         "arc4_crypt": (c_int, [c_sz, c_u8p, c_u8p, c_u8p]),
@@ -177,6 +194,8 @@ def _declare_gpu(lib):
         "otc_last_error": (ctypes.c_char_p, []),
         "otc_pick_impl": (c_int, [c_int, c_int, c_int, c_u64]),
         "otc_last_impl": (c_int, []),
+        "otc_xts_key_init": (c_int, [P(OtcXtsKey), c_u8p, c_int, c_int]),
+        "otc_aes_xts": (c_int, [c_vp, c_vp, c_sz, c_sz, P(OtcXtsKey), c_u8p, c_vp]),
         "otc_split_stats": (None, [c_int]),
         "otc_split_fallback_reason": (ctypes.c_char_p, []),
         "otc_split_last_units": (c_int, [ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]),

@@ -130,3 +130,33 @@ class AES:
         if segment_bytes:
             return cpu_ref.cfb128_segments(self._key, iv, data, segment_bytes)
         return cpu_ref.serial_encrypt("cfb128", self._key, iv, data)
+
+
+class AESXTS:
+    """XTS-AES (IEEE 1619) sector cipher: ``key`` is K1 || K2, 32 bytes
+    (AES-128) or 64 (AES-256).  Data units of ``unit_bytes`` use tweak numbers
+    ``tweak0``, ``tweak0 + 1``, ... (ints, or 16 bytes as a 128-bit
+    little-endian number); ``unit_bytes=None`` takes the data as one unit of
+    any length from 16 bytes (ciphertext stealing).  GPU tensors go to the HIP
+    kernels (in place allowed), ``bytes`` to the C oracle."""
+
+    def __init__(self, key: bytes):
+        key = bytes(key)
+        if len(key) not in (32, 64):
+            raise ValueError("Invalid XTS key size (K1 || K2: 32 or 64 bytes).")
+        self._key = key
+
+    @property
+    def key_bits(self) -> int:
+        """Bits of each AES key half."""
+        return len(self._key) * 4
+
+    def encrypt(self, data, tweak0, unit_bytes: int | None = None, out=None):
+        if isinstance(data, torch.Tensor):
+            return ops.xts_encrypt(data, self._key, tweak0, unit_bytes, out=out)
+        return cpu_ref.xts(self._key, tweak0, data, unit_bytes)
+
+    def decrypt(self, data, tweak0, unit_bytes: int | None = None, out=None):
+        if isinstance(data, torch.Tensor):
+            return ops.xts_decrypt(data, self._key, tweak0, unit_bytes, out=out)
+        return cpu_ref.xts(self._key, tweak0, data, unit_bytes, decrypt=True)

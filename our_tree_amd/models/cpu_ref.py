@@ -104,6 +104,45 @@ def cfb128_segments(key: bytes, iv0: bytes, data: bytes, segment_bytes: int, dec
     return bytes(out)
 
 
+def xts_tweak(tweak0) -> bytes:
+    """A tweak number as its 16 little-endian bytes (an int modulo 2**128, or
+    16 bytes taken as they are)."""
+    if isinstance(tweak0, int):
+        return (tweak0 % (1 << 128)).to_bytes(16, "little")
+    tweak0 = bytes(tweak0)
+    if len(tweak0) != 16:
+        raise ValueError("tweak0 must be an int or 16 bytes")
+    return tweak0
+
+
+def xts(key: bytes, tweak0, data: bytes, unit_bytes: int | None = None, decrypt: bool = False) -> bytes:
+    """XTS-AES (IEEE 1619) over data units of ``unit_bytes`` (None: the data
+    is one unit); unit s uses tweak number ``tweak0 + s`` (128-bit
+    little-endian).  ``key`` is K1 || K2, 32 or 64 bytes.  A single unit may
+    have any length from 16 bytes (ciphertext stealing)."""
+    key, data = bytes(key), bytes(data)
+    if len(key) not in (32, 64):
+        raise ValueError("XTS key must be 32 or 64 bytes (K1 || K2)")
+    unit = len(data) if unit_bytes is None else int(unit_bytes)
+    if unit < 16 or len(data) % unit:
+        raise ValueError("unit_bytes must be at least 16 and divide the data")
+    nunits = len(data) // unit
+    if unit > 1 << 24 or (nunits > 1 and unit % 16):
+        raise ValueError("units of several must be multiples of 16 bytes, at most 2**20 blocks each")
+    lib = _native.cpu_lib()
+    ctx = _native.AesXtsContext()
+    rc = (lib.aes_xts_setkey_dec if decrypt else lib.aes_xts_setkey_enc)(ctypes.byref(ctx), _native.as_u8p(key),
+                                                                       len(key) * 8)
+    if rc:
+        raise ValueError("invalid XTS key length")
+    out = _buf(len(data))
+    rc = lib.aes_crypt_xts_units(ctypes.byref(ctx), AES_DECRYPT if decrypt else AES_ENCRYPT, unit, nunits,
+                                 _native.as_u8p(xts_tweak(tweak0)), _native.as_u8p(data), out)
+    if rc:
+        raise ValueError("invalid XTS length")
+    return bytes(out)[: len(data)]
+
+
 def serial_encrypt(mode: str, key: bytes, iv: bytes, data: bytes) -> bytes:
     """Exact single-stream CBC / CFB128 encryption on one core with AES-NI
     (the C oracle where AES-NI is absent).  This is the host path for the

@@ -10,11 +10,12 @@ buffers.  Reference kernels: /root/reference/aes-gpu/Source/AES.cu:284-502
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
 from .. import _native
-from .keys import expand_key
+from .keys import DECRYPT, ENCRYPT, expand_key
 
 IMPLS = {"auto": 0, "ttable": 1, "bitslice": 2, "split": 3}  # otc.h OTC_IMPL_*
 
@@ -547,6 +548,60 @@ def cfb128_decrypt(x: torch.Tensor, key: bytes, iv: bytes, out=None, impl="auto"
             _b16(iv, "iv"), _impl(impl), _stream(x)), inplace_ok=False)
     _native.check(rc, "otc_aes_cfb128_decrypt")
     return out
+
+
+XTS_MAX_UNIT = 1 << 24  # bytes: 2**20 blocks, the IEEE 1619 limit
+
+
+@functools.lru_cache(maxsize=64)
+def _xts_key(key: bytes, direction: int) -> _native.OtcXtsKey:
+    k = _native.OtcXtsKey()
+    _native.check(_lib().otc_xts_key_init(ctypes.byref(k), _native.as_u8p(key), len(key) * 8, direction),
+                  "otc_xts_key_init")
+    return k
+
+
+def _xts_tweak(tweak0) -> ctypes.Array:
+    """A tweak number as 16 little-endian bytes (an int modulo 2**128, or 16 bytes as they are)."""
+    if isinstance(tweak0, int):
+        tweak0 = (tweak0 % (1 << 128)).to_bytes(16, "little")
+    return _b16(tweak0, "tweak0")
+
+
+def _xts(x: torch.Tensor, key: bytes, tweak0, unit_bytes, out, decrypt: bool) -> torch.Tensor:
+    _check_dev(x, "x")
+    key = bytes(key)
+    if len(key) not in (32, 64):
+        raise ValueError(f"XTS key must be 32 or 64 bytes (K1 || K2), got {len(key)}")
+    n = _nbytes(x)
+    unit = n if unit_bytes is None else int(unit_bytes)
+    if unit < 16 or unit > XTS_MAX_UNIT or n % unit:
+        raise ValueError("an XTS data unit is 16 bytes to 16 MiB and divides the byte size")
+    if n // unit > 1 and unit % 16:
+        raise ValueError("XTS data units of several must be multiples of 16 bytes")
+    tw = _xts_tweak(tweak0)
+    out = _out_like(x, out)
+    k = _xts_key(key, DECRYPT if decrypt else ENCRYPT)
+    with torch.cuda.device(x.device):
+        rc = _run(x, out, lambda ip, op: _lib().otc_aes_xts(ip, op, unit, n // unit, ctypes.byref(k), tw, _stream(x)))
+    _native.check(rc, "otc_aes_xts")
+    return out
+
+
+def xts_encrypt(x: torch.Tensor, key: bytes, tweak0, unit_bytes: int | None = None, out=None) -> torch.Tensor:
+    """XTS-AES (IEEE 1619) encryption of data units (sectors) of ``unit_bytes``
+    each; ``None`` takes the whole tensor as one unit, which may then have any
+    length from 16 bytes (ciphertext stealing).  ``key`` is K1 || K2 (32 or 64
+    bytes); unit s uses tweak number ``tweak0 + s`` -- an int, or 16 bytes read
+    as a 128-bit little-endian number (dm-crypt plain64: the sector number).
+    Fully parallel; may run in place; the grid T-table kernels of
+    ``csrc/hip/aes_xts.hip`` (``last_impl() == "ttable"``)."""
+    return _xts(x, key, tweak0, unit_bytes, out, False)
+
+
+def xts_decrypt(x: torch.Tensor, key: bytes, tweak0, unit_bytes: int | None = None, out=None) -> torch.Tensor:
+    """Inverse of ``xts_encrypt`` (as parallel, and also allowed in place)."""
+    return _xts(x, key, tweak0, unit_bytes, out, True)
 
 
 def _seg_call(fn_name: str, x: torch.Tensor, key: bytes, iv0: bytes, segment_bytes: int, out, inplace_ok: bool,
