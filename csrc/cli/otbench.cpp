@@ -4,7 +4,7 @@
  * per configuration.
  *
  *   otbench --mode ctr|ecb|ecb-dec|cbc-dec|cbc-enc-seg|cfb-enc-seg|cfb-dec-seg|cbc-dec-seg|cfb-dec|ctr-stream|xor|rc4
- *                  |ecb-split|ecbdec-split|cbcdec-split|cfbdec-split|ctr-split|xts-enc|xts-dec
+ *                  |ecb-split|ecbdec-split|cbcdec-split|cfbdec-split|ctr-split|xts-enc|xts-dec|gcm-enc|gcm-dec
  *           [--bits 128] [--bytes 1G] [--iters 20] [--warmup 3]
  *           [--impl auto|ttable|bitslice|split] [--inplace] [--verify] [--clock]
  *           [--mark]                        "OTB_MARK start|end" on stderr around the timed loop
@@ -18,6 +18,10 @@
  *           [--seg 4096]                    CBC segment size
  *           [--unit 4096]                   xts-enc / xts-dec: bytes per data unit (a multiple of 16);
  *                                           --bits 128|256 is the size of each key half
+ *           [--aad 0] [--ivlen 12]          gcm-enc / gcm-dec: bytes of additional authenticated data and of
+ *                                           the IV (>= 1; 12 is GCM's fast path).  --bytes may be any byte
+ *                                           count; --verify also recomputes the tag on the host, and the JSON
+ *                                           line carries "tag" and "tag_ok"
  *           [--share 0.2]                   *-split: the bitsliced kernel's share of the
  *                                           blocks, run CONCURRENTLY with the T-table kernel
  *                                           on the rest (two streams, co-resident per CU) --
@@ -78,6 +82,7 @@ struct Cfg {
     size_t seg = 4096;
     double share = 0.2;
     size_t streams = 65536, len = 4096, keylen = 16, drop = 0;
+    size_t aad = 0, ivlen = 12; /* gcm-enc / gcm-dec */
 };
 
 struct OpArg {
@@ -85,6 +90,9 @@ struct OpArg {
     void *in, *out;
     otc_aes_key *k;
     otc_xts_key *xk; /* xts-enc / xts-dec */
+    otc_gcm_key *gk; /* gcm-enc / gcm-dec: key, IV, AAD and 16 device bytes for the computed tag */
+    std::vector<uint8_t> giv, gaad;
+    void *tag_dev;
     uint8_t iv[16];
     uint8_t *keys;
     void *sa, *sb; /* *-split: T-table / bitsliced streams */
@@ -92,6 +100,7 @@ struct OpArg {
 };
 
 static bool is_xts(const std::string &m) { return m == "xts-enc" || m == "xts-dec"; }
+static bool is_gcm(const std::string &m) { return m == "gcm-enc" || m == "gcm-dec"; }
 
 static bool is_split(const std::string &m)
 {
@@ -159,6 +168,9 @@ static int run_op(void *p)
     if (c.mode == "cfb-dec") return otc_aes_cfb128_decrypt_impl(a->in, a->out, c.bytes, a->k, a->iv, c.impl, nullptr);
     if (is_xts(c.mode)) /* --unit BYTES per data unit, tweak0 = iv as a little-endian number */
         return otc_aes_xts(a->in, a->out, c.seg, c.bytes / c.seg, a->xk, a->iv, nullptr);
+    if (is_gcm(c.mode))
+        return otc_aes_gcm(a->in, a->out, c.bytes, a->gk, c.mode == "gcm-dec" ? OTC_DIR_DECRYPT : OTC_DIR_ENCRYPT,
+                           a->giv.data(), a->giv.size(), a->gaad.data(), a->gaad.size(), a->tag_dev, c.impl, nullptr);
     if (c.mode == "xor") return otc_xor(a->in, a->out, a->out, c.bytes, nullptr);
     if (c.mode == "rc4") return otc_rc4_multi(a->keys, (int)c.keylen, c.streams, c.len, c.drop, a->in, a->out, nullptr);
     return OTC_ERR_ARG;
@@ -243,7 +255,15 @@ static bool snapshot(const Cfg &c, const OpArg &a, CopyFn cp, std::vector<Sample
 }
 
 /* the oracle's output for one sample; false if the mode has no oracle */
-static bool oracle(const Cfg &c, const uint8_t key[64], const uint8_t iv0[16], const Sample &s, std::vector<uint8_t> &ref)
+/* J0 and the hash key of a gcm-* run, from the key and the IV */
+static void gcm_setup(const Cfg &c, const uint8_t *key, const std::vector<uint8_t> &iv, aes_gcm_context &g, uint8_t j0[16])
+{
+    aes_gcm_setkey(&g, key, c.bits);
+    aes_gcm_j0(&g, iv.data(), iv.size(), j0);
+}
+
+static bool oracle(const Cfg &c, const uint8_t key[64], const uint8_t iv0[16], const std::vector<uint8_t> &giv,
+                   const Sample &s, std::vector<uint8_t> &ref)
 {
     ref.assign(s.len, 0);
     const uint8_t *in = s.in.data() + s.pre;
@@ -255,6 +275,16 @@ static bool oracle(const Cfg &c, const uint8_t key[64], const uint8_t iv0[16], c
         memcpy(nc, iv0, 16);
         aes_ctr128_add(nc, s.off / 16);
         aes_ctr_bulk(&ctx, nc, in, ref.data(), s.len, 8);
+    } else if (is_gcm(m)) {
+        /* both directions XOR the CTR32 stream from inc32(J0): the block at byte s.off has counter
+         * low word J0 + 1 + s.off / 16 modulo 2^32, the upper 96 bits those of J0 */
+        aes_gcm_context g;
+        uint8_t ctr[16];
+        gcm_setup(c, key, giv, g, ctr);
+        uint32_t lo = ((uint32_t)ctr[12] << 24) | ((uint32_t)ctr[13] << 16) | ((uint32_t)ctr[14] << 8) | ctr[15];
+        lo += 1u + (uint32_t)(s.off / 16);
+        for (int i = 0; i < 4; ++i) ctr[12 + i] = (uint8_t)(lo >> (24 - 8 * i));
+        aes_crypt_ctr32(&g, s.len, ctr, in, ref.data());
     } else if (m == "ctr-stream") {
         /* the run's context: nc_off 15 with a zero stream block, so data byte 0
          * passes through and byte p >= 1 uses keystream byte (p - 1) of the
@@ -343,7 +373,7 @@ static int check_samples(const Cfg &c, const OpArg &a, CopyFn cp, const uint8_t 
     for (const Sample &s : samples) {
         std::vector<uint8_t> got(s.len), ref;
         if (cp(got.data(), (const uint8_t *)a.out + s.off, s.len)) return -1;
-        if (!oracle(c, key, a.iv, s, ref)) return -1;
+        if (!oracle(c, key, a.iv, a.giv, s, ref)) return -1;
         if (memcmp(got.data(), ref.data(), s.len) != 0) {
             size_t i = 0;
             while (got[i] == ref[i]) ++i;
@@ -385,6 +415,37 @@ static void mark(const char *what)
     fflush(stderr);
 }
 
+/* GHASH continued over n bytes of the buffers under test (n a multiple of 16 unless it ends the data),
+ * copied to the host in pieces */
+static bool ghash_buffer(const aes_gcm_context &g, uint8_t y[16], const void *buf, size_t n, CopyFn cp)
+{
+    std::vector<uint8_t> h(std::min<size_t>(n, 64u << 20));
+    for (size_t off = 0; off < n; off += h.size()) {
+        const size_t step = std::min(h.size(), n - off);
+        if (cp(h.data(), (const uint8_t *)buf + off, step)) return false;
+        aes_ghash(&g, y, h.data(), step);
+    }
+    return true;
+}
+
+/* the tag of a gcm-* run from the ciphertext in `ct`, by the definition: GHASH(AAD || C || lengths) ^ E_K(J0) */
+static bool gcm_expected_tag(const Cfg &c, const OpArg &a, const uint8_t *key, const void *ct, CopyFn cp, uint8_t tag[16])
+{
+    aes_gcm_context g;
+    uint8_t j0[16], y[16] = {0}, lb[16];
+    gcm_setup(c, key, a.giv, g, j0);
+    aes_ghash(&g, y, a.gaad.data(), a.gaad.size());
+    if (!ghash_buffer(g, y, ct, c.bytes, cp)) return false;
+    for (int i = 0; i < 8; ++i) {
+        lb[i] = (uint8_t)(((uint64_t)a.gaad.size() * 8) >> (56 - 8 * i));
+        lb[8 + i] = (uint8_t)(((uint64_t)c.bytes * 8) >> (56 - 8 * i));
+    }
+    aes_ghash(&g, y, lb, 16);
+    aes_crypt_ecb(&g.enc, AES_ENCRYPT, j0, tag);
+    for (int i = 0; i < 16; ++i) tag[i] ^= y[i];
+    return true;
+}
+
 static const char *verdict(bool asked, int v) { return !asked ? "null" : v == 1 ? "true" : "false"; }
 
 int main(int argc, char **argv)
@@ -418,6 +479,8 @@ int main(int argc, char **argv)
         else if (a == "--gpus") c.gpus = atoi(nx());
         else if (a == "--strategy") c.strategy = std::string(nx()) == "rccl" ? 1 : 0;
         else if (a == "--seg" || a == "--unit") c.seg = parse_size(nx());
+        else if (a == "--aad") c.aad = parse_size(nx());
+        else if (a == "--ivlen") c.ivlen = parse_size(nx());
         else if (a == "--share") c.share = atof(nx());
         else if (a == "--streams") c.streams = parse_size(nx());
         else if (a == "--len") c.len = parse_size(nx());
@@ -431,7 +494,7 @@ int main(int argc, char **argv)
     static const char *modes[] = {"ctr", "ecb", "ecb-dec", "cbc-dec", "cbc-enc-seg", "cfb-enc-seg", "cfb-dec-seg",
                                   "cbc-dec-seg",
                                   "cfb-dec", "ctr-stream", "xor", "rc4", "ecb-split", "ecbdec-split", "cbcdec-split",
-                                  "cfbdec-split", "ctr-split", "xts-enc", "xts-dec"};
+                                  "cfbdec-split", "ctr-split", "xts-enc", "xts-dec", "gcm-enc", "gcm-dec"};
     bool known = false;
     for (const char *m : modes) known |= c.mode == m;
     if (!known) {
@@ -439,7 +502,12 @@ int main(int argc, char **argv)
         return 2;
     }
     if (c.mode == "rc4") c.bytes = c.streams * c.len;
-    if (c.mode != "ctr" && c.mode != "ctr-stream" && c.mode != "xor" && c.mode != "rc4") c.bytes &= ~(size_t)15;
+    if (c.mode != "ctr" && c.mode != "ctr-stream" && c.mode != "xor" && c.mode != "rc4" && !is_gcm(c.mode))
+        c.bytes &= ~(size_t)15;
+    if (is_gcm(c.mode) && (c.ivlen == 0 || c.bytes > AES_GCM_MAX_BYTES)) {
+        fprintf(stderr, "gcm: --ivlen is at least 1, --bytes at most 2^36 - 32\n");
+        return 2;
+    }
     if (is_seg_mode(c.mode)) {
         if (c.seg == 0 || c.seg % 16) {
             fprintf(stderr, "--seg / --unit must be a positive multiple of 16\n");
@@ -480,10 +548,22 @@ int main(int argc, char **argv)
         fprintf(stderr, "key: %s\n", otc_last_error());
         return 1;
     }
+    otc_gcm_key gk;
+    if (is_gcm(c.mode) && otc_gcm_key_init(&gk, key, c.bits)) {
+        fprintf(stderr, "key: %s\n", otc_last_error());
+        return 1;
+    }
     OpArg a{};
     a.c = &c;
     a.k = &k;
     a.xk = &xk;
+    a.gk = &gk;
+    if (is_gcm(c.mode)) {
+        a.giv.resize(c.ivlen);
+        a.gaad.resize(c.aad);
+        for (size_t i = 0; i < c.ivlen; ++i) a.giv[i] = (uint8_t)(0xF0 + i);
+        for (size_t i = 0; i < c.aad; ++i) a.gaad[i] = (uint8_t)(7 * i + 3);
+    }
     for (int i = 0; i < 16; ++i) a.iv[i] = (uint8_t)(0xF0 + i);
 
     const int cus = otc_device_cus(0);
@@ -558,6 +638,10 @@ int main(int argc, char **argv)
     }
     otc_fill_random(a.in, c.bytes, 42, nullptr);
     if (!c.inplace) otc_fill_random(a.out, c.bytes, 43, nullptr);
+    if (is_gcm(c.mode) && !(a.tag_dev = otc_dev_malloc(16))) {
+        fprintf(stderr, "device alloc failed: %s\n", otc_last_error());
+        return 1;
+    }
     if (c.mode == "rc4") {
         a.keys = (uint8_t *)otc_dev_malloc(c.streams * c.keylen);
         otc_fill_random(a.keys, c.streams * c.keylen, 44, nullptr);
@@ -573,9 +657,13 @@ int main(int argc, char **argv)
         }
     }
     int v = -1;
+    uint8_t tag[16] = {0}, want_tag[16] = {0};
+    int tag_ok = -1; /* gcm-* with --verify: the device's tag against the host's */
     if (c.verify) {
         /* the inputs of the samples are copied BEFORE the op: valid in place */
         std::vector<Sample> samples;
+        /* the tag is over the ciphertext: the input of a decryption, hashed before the op overwrites it */
+        if (c.mode == "gcm-dec" && !gcm_expected_tag(c, a, key, a.in, copy_d2h, want_tag)) return 1;
         if (!snapshot(c, a, copy_d2h, samples)) {
             fprintf(stderr, "verify snapshot: %s\n", otc_last_error());
             return 1;
@@ -586,6 +674,15 @@ int main(int argc, char **argv)
         }
         if (c.corrupt_at >= 0 && corrupt(a.out, (size_t)c.corrupt_at, true)) return 1;
         v = check_samples(c, a, copy_d2h, key, samples);
+        if (is_gcm(c.mode)) {
+            if (c.mode == "gcm-enc" && !gcm_expected_tag(c, a, key, a.out, copy_d2h, want_tag)) return 1;
+            if (otc_memcpy(tag, a.tag_dev, 16, OTC_D2H)) return 1;
+            tag_ok = memcmp(tag, want_tag, 16) == 0;
+            if (!tag_ok) {
+                fprintf(stderr, "verify: %s tag mismatch\n", c.mode.c_str());
+                if (v == 1) v = 0;
+            }
+        }
     }
     for (int w = 0; w < c.warmup; ++w)
         if (run_op(&a)) {
@@ -655,13 +752,20 @@ int main(int argc, char **argv)
         fprintf(stderr, "clock: %s\n", otc_last_error());
         return 1;
     }
-    char clk[320] = "";
+    char clk[512] = "";
     if (c.clock)
         snprintf(clk, sizeof clk, "\"held_clock_ghz\": %.3f, \"cycles_per_byte_per_cu_held\": %.3f, ", held,
                  (ms * 1e-3) * held * 1e9 * cus / (double)c.bytes);
     strncat(clk, split_units, sizeof clk - strlen(clk) - 1);
     if (c.mode.size() > 6 && c.mode.compare(c.mode.size() - 6, 6, "-split") == 0)
         snprintf(clk + strlen(clk), sizeof clk - strlen(clk), "\"share\": %.3f, ", c.share);
+    if (is_gcm(c.mode)) { /* the tag of the last call (with --verify: of the verified one, read before the timed loop) */
+        if (!c.verify && (otc_device_sync() || otc_memcpy(tag, a.tag_dev, 16, OTC_D2H))) return 1;
+        char hex[33];
+        for (int i = 0; i < 16; ++i) snprintf(hex + 2 * i, 3, "%02x", tag[i]);
+        snprintf(clk + strlen(clk), sizeof clk - strlen(clk), "\"aad\": %zu, \"ivlen\": %zu, \"tag\": \"%s\", \"tag_ok\": %s, ",
+                 c.aad, c.ivlen, hex, tag_ok < 0 ? "null" : tag_ok ? "true" : "false");
+    }
     const int ran = otc_last_impl(); /* what the last timed call ran (this thread) */
     printf("{\"mode\": \"%s\", \"bits\": %d, \"bytes\": %zu, \"impl\": \"%s\", \"ran\": \"%s\", \"inplace\": %s, "
            "\"iters\": %d, \"ms\": %.4f, \"gbps\": %.2f, \"cycles_per_byte_per_cu\": %.3f, \"cus\": %d, \"clock_mhz\": %.0f, %s"
@@ -676,6 +780,7 @@ int main(int argc, char **argv)
     otc_dev_free(a.in);
     if (!c.inplace) otc_dev_free(a.out);
     otc_dev_free(a.keys);
+    otc_dev_free(a.tag_dev);
     otc_stream_destroy(a.sa);
     otc_stream_destroy(a.sb);
     return (c.verify && v != 1) ? 3 : 0;

@@ -226,6 +226,45 @@ int otc_aes_xts(const void *in, void *out, size_t unit, size_t nunits, const otc
                : OTC_OK;
 }
 
+int otc_gcm_key_init(otc_gcm_key *k, const uint8_t *key, int keybits)
+{
+    aes_gcm_context g;
+    if (aes_gcm_setkey(&g, key, (unsigned)keybits)) return fail(OTC_ERR_ARG, "invalid AES key size");
+    memcpy(k->h, g.h, 16);
+    return otc_aes_key_init(&k->enc, key, keybits, OTC_DIR_ENCRYPT);
+}
+
+int otc_aes_ctr32(const void *in, void *out, size_t n, const otc_aes_key *k, const uint8_t ctr0[16], int, void *)
+{
+    if (n > ((uint64_t)1 << 36)) return fail(OTC_ERR_ARG, "ctr32: more than 2^32 blocks");
+    aes_gcm_context g;
+    aes_import_rk32(&g.enc, k->rk, k->nr);
+    uint8_t c[16];
+    memcpy(c, ctr0, 16);
+    return aes_crypt_ctr32(&g, n, c, (const uint8_t *)in, (uint8_t *)out);
+}
+
+int otc_ghash(const void *data, size_t n, const uint8_t h[16], const uint8_t y0[16], void *y_dev, void *)
+{
+    aes_gcm_context g;
+    aes_gcm_set_h(&g, h);
+    memcpy(y_dev, y0, 16);
+    aes_ghash(&g, (uint8_t *)y_dev, (const uint8_t *)data, n);
+    return OTC_OK;
+}
+
+int otc_aes_gcm(const void *in, void *out, size_t n, const otc_gcm_key *k, int dir, const uint8_t *iv, size_t iv_len,
+                const uint8_t *aad, size_t aad_len, void *tag_dev, int, void *)
+{
+    aes_gcm_context g;
+    aes_import_rk32(&g.enc, k->enc.rk, k->enc.nr);
+    aes_gcm_set_h(&g, k->h);
+    return aes_crypt_gcm(&g, dir == OTC_DIR_ENCRYPT ? AES_ENCRYPT : AES_DECRYPT, n, iv, iv_len, aad, aad_len,
+                         (const uint8_t *)in, (uint8_t *)out, (uint8_t *)tag_dev)
+               ? fail(OTC_ERR_ARG, "gcm lengths")
+               : OTC_OK;
+}
+
 int otc_xor(const void *a, const void *b, void *out, size_t n, void *)
 {
     for (size_t i = 0; i < n; ++i) ((uint8_t *)out)[i] = ((const uint8_t *)a)[i] ^ ((const uint8_t *)b)[i];

@@ -543,6 +543,230 @@ int aes_crypt_xts_units(aes_xts_context *ctx, int mode, size_t unit_bytes, size_
 }
 
 /* ---------------------------------------------------------------------------
+ * AES-GCM (NIST SP 800-38D), written from the standard.  A block is an
+ * element of GF(2^128) with its LEFTMOST bit (bit 7 of byte 0) the coefficient
+ * of x^0, so "times x" is a one-bit right shift of the 16-byte string, and a
+ * bit shifted out of byte 15 is folded back as R = 0xE1 || 0^120.
+ * GHASH's multiplications by H go through positional tables: tab[p][n] is
+ * (nibble n at nibble position p, everything else zero) . H, each a sum of the
+ * products H . x^i, and X . H the sum of 32 entries with no reduction step.
+ * The device tables (csrc/hip/aes_gcm.hip) are the byte form of the same.
+ * ------------------------------------------------------------------------- */
+static void gf128_mulx(unsigned char v[16])
+{
+    const unsigned carry = v[15] & 1u;
+    for (int i = 15; i > 0; --i) v[i] = (unsigned char)((v[i] >> 1) | (v[i - 1] << 7));
+    v[0] >>= 1;
+    if (carry) v[0] ^= 0xE1;
+}
+
+void aes_gf128_mul(unsigned char z[16], const unsigned char x[16], const unsigned char y[16])
+{
+    unsigned char v[16], acc[16] = {0};
+    memcpy(v, y, 16);
+    for (int i = 0; i < 128; ++i) {
+        if (x[i / 8] & (0x80u >> (i % 8)))
+            for (int j = 0; j < 16; ++j) acc[j] ^= v[j];
+        gf128_mulx(v);
+    }
+    memcpy(z, acc, 16);
+}
+
+void aes_gcm_set_h(aes_gcm_context *ctx, const unsigned char h[16])
+{
+    unsigned char p[128][16]; /* H . x^i */
+    memcpy(ctx->h, h, 16);
+    memcpy(p[0], h, 16);
+    for (int i = 1; i < 128; ++i) {
+        memcpy(p[i], p[i - 1], 16);
+        gf128_mulx(p[i]);
+    }
+    for (int pos = 0; pos < 32; ++pos)
+        for (int n = 0; n < 16; ++n) {
+            unsigned char e[16] = {0};
+            for (int k = 0; k < 4; ++k) /* the nibble's leftmost bit is the lowest power */
+                if (n & (8 >> k))
+                    for (int j = 0; j < 16; ++j) e[j] ^= p[4 * pos + k][j];
+            memcpy(ctx->tab[pos][n], e, 16);
+        }
+}
+
+int aes_gcm_setkey(aes_gcm_context *ctx, const unsigned char *key, unsigned int keybits)
+{
+    const int r = aes_setkey_enc(&ctx->enc, key, keybits);
+    if (r) return r;
+    unsigned char h[16] = {0};
+    /* this copy's tables: in a process that holds two copies of this file
+     * (libotc.so loaded globally, then libotc_cpu.so) the call above may have
+     * run in the other one, and encrypt_block is this one's */
+    ensure_tables();
+    encrypt_block(&ctx->enc, h, h);
+    aes_gcm_set_h(ctx, h);
+    return 0;
+}
+
+/* y = y . H */
+static void ghash_mul_h(const aes_gcm_context *ctx, unsigned char y[16])
+{
+    uint64_t a = 0, b = 0;
+    for (int i = 0; i < 16; ++i) {
+        const uint64_t *hi = ctx->tab[2 * i][y[i] >> 4], *lo = ctx->tab[2 * i + 1][y[i] & 15];
+        a ^= hi[0] ^ lo[0];
+        b ^= hi[1] ^ lo[1];
+    }
+    memcpy(y, &a, 8);
+    memcpy(y + 8, &b, 8);
+}
+
+static void ghash_serial(const aes_gcm_context *ctx, unsigned char y[16], const unsigned char *data, size_t len)
+{
+    while (len) {
+        const size_t n = len < 16 ? len : 16;
+        for (size_t i = 0; i < n; ++i) y[i] ^= data[i];
+        ghash_mul_h(ctx, y);
+        data += n;
+        len -= n;
+    }
+}
+
+typedef struct {
+    const aes_gcm_context *ctx;
+    const unsigned char *data;
+    size_t len;
+    unsigned char y[16];
+} ghash_job;
+
+static void *ghash_worker(void *arg)
+{
+    ghash_job *j = (ghash_job *)arg;
+    ghash_serial(j->ctx, j->y, j->data, j->len);
+    return NULL;
+}
+
+/* Large calls (the device tests' oracle) hash T pieces of whole blocks on T
+ * threads, piece 0 from y and the others from 0, and join them as
+ * Y = sum P_t . H^(blocks after piece t). */
+void aes_ghash(const aes_gcm_context *ctx, unsigned char y[16], const unsigned char *data, size_t len)
+{
+    enum { MAXT = 8 };
+    if (len < ((size_t)4 << 20)) {
+        ghash_serial(ctx, y, data, len);
+        return;
+    }
+    const size_t nblocks = (len + 15) / 16, per = nblocks / MAXT;
+    ghash_job jobs[MAXT];
+    pthread_t th[MAXT];
+    for (size_t t = 0; t < MAXT; ++t) {
+        const size_t first = t * per, end = t + 1 == MAXT ? nblocks : first + per;
+        jobs[t].ctx = ctx;
+        jobs[t].data = data + 16 * first;
+        jobs[t].len = t + 1 == MAXT ? len - 16 * first : 16 * (end - first);
+        memset(jobs[t].y, 0, 16);
+    }
+    memcpy(jobs[0].y, y, 16);
+    for (size_t t = 1; t < MAXT; ++t) pthread_create(&th[t], NULL, ghash_worker, &jobs[t]);
+    ghash_worker(&jobs[0]);
+    for (size_t t = 1; t < MAXT; ++t) pthread_join(th[t], NULL);
+    memset(y, 0, 16);
+    for (size_t t = 0; t < MAXT; ++t) {
+        /* H^after by square and multiply; after == 0 leaves the piece as it is */
+        size_t after = t + 1 == MAXT ? 0 : nblocks - (t + 1) * per;
+        unsigned char p[16], sq[16];
+        memcpy(p, jobs[t].y, 16);
+        memcpy(sq, ctx->h, 16);
+        for (; after; after >>= 1) {
+            if (after & 1) aes_gf128_mul(p, p, sq);
+            aes_gf128_mul(sq, sq, sq);
+        }
+        for (int i = 0; i < 16; ++i) y[i] ^= p[i];
+    }
+}
+
+static void gcm_inc32(unsigned char ctr[16])
+{
+    for (int i = 15; i >= 12; --i)
+        if (++ctr[i]) break;
+}
+
+int aes_crypt_ctr32(aes_gcm_context *ctx, size_t length, unsigned char ctr[16], const unsigned char *input,
+                    unsigned char *output)
+{
+    unsigned char ks[16];
+    ensure_tables();
+    while (length) {
+        const size_t n = length < 16 ? length : 16;
+        encrypt_block(&ctx->enc, ctr, ks);
+        gcm_inc32(ctr);
+        for (size_t i = 0; i < n; ++i) output[i] = (unsigned char)(input[i] ^ ks[i]);
+        input += n;
+        output += n;
+        length -= n;
+    }
+    return 0;
+}
+
+static void gcm_put64(unsigned char *p, uint64_t v)
+{
+    for (int i = 0; i < 8; ++i) p[i] = (unsigned char)(v >> (56 - 8 * i));
+}
+
+void aes_gcm_j0(const aes_gcm_context *ctx, const unsigned char *iv, size_t iv_len, unsigned char j0[16])
+{
+    memset(j0, 0, 16);
+    if (iv_len == 12) {
+        memcpy(j0, iv, 12);
+        j0[15] = 1;
+        return;
+    }
+    unsigned char lb[16] = {0};
+    gcm_put64(lb + 8, (uint64_t)iv_len * 8);
+    aes_ghash(ctx, j0, iv, iv_len);
+    aes_ghash(ctx, j0, lb, 16);
+}
+
+int aes_crypt_gcm(aes_gcm_context *ctx, int mode, size_t length, const unsigned char *iv, size_t iv_len,
+                  const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                  unsigned char tag[16])
+{
+    if (iv_len == 0 || (uint64_t)length > AES_GCM_MAX_BYTES || (uint64_t)aad_len >> 61 || (uint64_t)iv_len >> 61)
+        return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    unsigned char j0[16], ekj0[16], ctr[16], y[16] = {0}, lb[16];
+    ensure_tables();
+    aes_gcm_j0(ctx, iv, iv_len, j0);
+    encrypt_block(&ctx->enc, j0, ekj0);
+    memcpy(ctr, j0, 16);
+    gcm_inc32(ctr);
+    aes_ghash(ctx, y, aad, aad_len);
+    /* the hash is over the ciphertext: before decrypting it, after producing
+     * it, so that input == output works in both directions */
+    if (mode == AES_DECRYPT) aes_ghash(ctx, y, input, length);
+    aes_crypt_ctr32(ctx, length, ctr, input, output);
+    if (mode != AES_DECRYPT) aes_ghash(ctx, y, output, length);
+    gcm_put64(lb, (uint64_t)aad_len * 8);
+    gcm_put64(lb + 8, (uint64_t)length * 8);
+    aes_ghash(ctx, y, lb, 16);
+    for (int i = 0; i < 16; ++i) tag[i] = (unsigned char)(y[i] ^ ekj0[i]);
+    return 0;
+}
+
+int aes_gcm_auth_decrypt(aes_gcm_context *ctx, size_t length, const unsigned char *iv, size_t iv_len,
+                         const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
+                         const unsigned char *input, unsigned char *output)
+{
+    if (tag_len < 4 || tag_len > 16) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    unsigned char t[16];
+    const int r = aes_crypt_gcm(ctx, AES_DECRYPT, length, iv, iv_len, aad, aad_len, input, output, t);
+    if (r) return r;
+    unsigned diff = 0; /* every byte compared, whatever the earlier ones gave */
+    for (size_t i = 0; i < tag_len; ++i) diff |= (unsigned)(t[i] ^ tag[i]);
+    if (diff) {
+        memset(output, 0, length);
+        return POLARSSL_ERR_GCM_AUTH_FAILED;
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------
  * Self test: FIPS-197 appendix C, SP 800-38A F.1/F.2/F.3/F.5, RFC 3686 #1-#3,
  * and the 10,000-iteration Monte-Carlo ECB/CBC chains of the NIST
  * rijndael-vals set that the reference's self-test runs

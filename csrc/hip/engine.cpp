@@ -540,6 +540,123 @@ extern "C" int otc_aes_xts(const void *in, void *out, size_t unit_bytes, size_t 
     return OTC_OK;
 }
 
+/* ---- GCM: CTR32, GHASH, the authenticated mode ---------------------------- */
+/* GCM's counter: the low 32 bits wrap, the upper 96 never change.  Up to the
+ * wrap the CTR kernels' 128-bit add cannot carry out of the low word, so the
+ * call is ctr_common as it is, twice when it crosses the wrap. */
+static int ctr32_run(const void *in, void *out, size_t nbytes, const otc_aes_key *k, const uint8_t ctr0[16], int impl,
+                     void *stream)
+{
+    if (!ctr0) return set_err(OTC_ERR_ARG, "null counter");
+    if (nbytes > ((uint64_t)1 << 36)) return set_err(OTC_ERR_ARG, "ctr32: more than 2^32 blocks");
+    if (int r = check_bufs(in, out, nbytes, true, "aes_ctr32")) return r; /* the whole range, before any launch */
+    const Ctr128 c = ctr_from_bytes(ctr0);
+    const uint64_t to_wrap = ((uint64_t)1 << 32) - (c.lo & 0xFFFFFFFFull); /* blocks before the low word is 0 again */
+    if ((nbytes + 15) / 16 <= to_wrap) return ctr_common(in, out, nbytes, k, c, false, impl, stream);
+    const size_t head = (size_t)to_wrap * 16;
+    if (int r = ctr_common(in, out, head, k, c, false, impl, stream)) return r;
+    const Ctr128 c2{c.hi, c.lo & ~0xFFFFFFFFull};
+    return ctr_common((const uint8_t *)in + head, (uint8_t *)out + head, nbytes - head, k, c2, false, impl, stream);
+}
+
+extern "C" int otc_aes_ctr32(const void *in, void *out, size_t nbytes, const otc_aes_key *k, const uint8_t ctr0[16],
+                             int impl, void *stream)
+{
+    Range rg("otc_aes_ctr32");
+    return ctr32_run(in, out, nbytes, k, ctr0, impl, stream);
+}
+
+extern "C" int otc_ghash_spans(uint64_t *spans, int max)
+{
+    uint64_t none;
+    return otc_impl::ghash_spans(spans ? spans : &none, spans ? max : 0);
+}
+
+extern "C" int otc_ghash(const void *data, size_t nbytes, const uint8_t h[16], const uint8_t y0[16], void *y_dev,
+                         void *stream)
+{
+    Range rg("otc_ghash");
+    if (!h || !y0 || !y_dev) return set_err(OTC_ERR_ARG, "null argument");
+    if ((uintptr_t)y_dev & 3u) return set_err(OTC_ERR_ARG, "ghash: the result must be 4-byte aligned");
+    if (nbytes > ((uint64_t)1 << 36)) return set_err(OTC_ERR_ARG, "ghash: more than 2^36 bytes");
+    if (nbytes && !data) return set_err(OTC_ERR_ARG, "ghash: null buffer");
+    if ((uintptr_t)data & 15u) return set_err(OTC_ERR_ARG, "ghash: device buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    void *ws = nullptr;
+    hipError_t e = otc_impl::ghash_ws_alloc(nbytes, st, &ws);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? set_err(OTC_ERR_NOMEM, "ghash: no memory for the tables and partials")
+                                        : hip_fail(e, "ghash workspace");
+    }
+    e = otc_impl::ghash_run(data, nbytes, h, y0, nullptr, nullptr, y_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, "ghash launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_gcm_key_init(otc_gcm_key *k, const uint8_t *key, int keybits)
+{
+    if (!k || !key) return set_err(OTC_ERR_ARG, "null argument");
+    aes_gcm_context g;
+    if (aes_gcm_setkey(&g, key, (unsigned)keybits)) return set_err(OTC_ERR_ARG, "invalid AES key size (must be 128/192/256)");
+    if (int r = otc_aes_key_init(&k->enc, key, keybits, OTC_DIR_ENCRYPT)) return r;
+    memcpy(k->h, g.h, 16);
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_gcm_key *k, int dir, const uint8_t *iv,
+                           size_t iv_len, const uint8_t *aad, size_t aad_len, void *tag_dev, int impl, void *stream)
+{
+    Range rg("otc_aes_gcm");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (!iv || iv_len == 0) return set_err(OTC_ERR_ARG, "gcm: the IV must have at least 1 byte");
+    if (aad_len && !aad) return set_err(OTC_ERR_ARG, "gcm: null aad");
+    if ((uint64_t)iv_len >> 61 || (uint64_t)aad_len >> 61) return set_err(OTC_ERR_ARG, "gcm: IV or AAD too long");
+    if (!tag_dev || ((uintptr_t)tag_dev & 3u)) return set_err(OTC_ERR_ARG, "gcm: the tag must be 4-byte aligned device memory");
+    if (nbytes > AES_GCM_MAX_BYTES) return set_err(OTC_ERR_ARG, "gcm: a message has at most 2^36 - 32 bytes");
+    if (int r = check_bufs(in, out, nbytes, true, "aes_gcm")) return r;
+    if (int r = check_impl(impl)) return r;
+    hipStream_t st = (hipStream_t)stream;
+
+    /* what does not depend on the data, on the host */
+    aes_gcm_context g;
+    aes_import_rk32(&g.enc, k->enc.rk, k->enc.nr);
+    aes_gcm_set_h(&g, k->h);
+    uint8_t j0[16], ekj0[16], ctr[16], y0[16] = {0}, lenblock[16];
+    aes_gcm_j0(&g, iv, iv_len, j0);
+    aes_crypt_ecb(&g.enc, AES_ENCRYPT, j0, ekj0);
+    memcpy(ctr, j0, 16);
+    for (int i = 15; i >= 12; --i)
+        if (++ctr[i]) break;
+    aes_ghash(&g, y0, aad, aad_len);
+    for (int i = 0; i < 8; ++i) {
+        lenblock[i] = (uint8_t)(((uint64_t)aad_len * 8) >> (56 - 8 * i));
+        lenblock[8 + i] = (uint8_t)(((uint64_t)nbytes * 8) >> (56 - 8 * i));
+    }
+
+    /* the hash's memory first: a failure leaves out and the tag untouched */
+    void *ws = nullptr;
+    hipError_t e = otc_impl::ghash_ws_alloc(nbytes, st, &ws);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? set_err(OTC_ERR_NOMEM, "gcm: no memory for the hash's tables and partials")
+                                        : hip_fail(e, "gcm workspace");
+    }
+    if (dir == OTC_DIR_ENCRYPT && nbytes) {
+        if (int r = ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream)) {
+            if (ws) (void)hipFreeAsync(ws, st);
+            return r;
+        }
+    }
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    e = otc_impl::ghash_run(dir == OTC_DIR_ENCRYPT ? out : in, nbytes, k->h, y0, lenblock, ekj0, tag_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm hash launch");
+    if (dir == OTC_DIR_DECRYPT && nbytes) return ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream);
+    return OTC_OK;
+}
+
 extern "C" int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream)
 {
     Range rg("otc_xor");

@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_bs.hip, stream_ops.hip), declared once: included by their callers
+ * aes_xts.hip, aes_gcm.hip, aes_bs.hip, stream_ops.hip), declared once: included by their callers
  * (engine.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
  * of the public C API (otc.h).
@@ -90,6 +90,20 @@ hipError_t xts_bulk(const void *in, void *out, uint64_t nblocks, uint32_t unit_b
  * (queued behind xts_bulk over its first m - 1 blocks) */
 hipError_t xts_steal(const void *in, void *out, uint32_t m, uint32_t r, const otc_aes_key &K1, const otc_aes_key &K2,
                      const uint8_t tweak0[16], hipStream_t st);
+
+/* ---- aes_gcm.hip --------------------------------------------------------- */
+/* byte sizes of the GHASH decomposition's pieces, smallest first; returns how many there are */
+int ghash_spans(uint64_t *spans, int max);
+/* whether the levels reach nbytes (they reach 2^37 bytes) */
+bool ghash_fits(uint64_t nbytes);
+/* the per-call tables and partials of ghash_run over nbytes, stream-ordered
+ * (behind otc_fault_inject_alloc); *ws stays null for nbytes == 0 */
+hipError_t ghash_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws);
+/* out16 (device) = GHASH_h continued from y0 over nbytes of device data, or,
+ * with lenblock and ekj0, the GCM tag ((Y ^ lenblock) . H) ^ ekj0.  Frees ws
+ * behind its kernels, also when it fails. */
+hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], const uint8_t y0[16],
+                     const uint8_t *lenblock, const uint8_t *ekj0, void *out16, void *ws, hipStream_t st);
 
 /* ---- aes_bs.hip ---------------------------------------------------------- */
 hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,

@@ -94,6 +94,40 @@ int aes_crypt_xts(aes_xts_context *ctx, int mode, size_t length, const unsigned 
 int aes_crypt_xts_units(aes_xts_context *ctx, int mode, size_t unit_bytes, size_t nunits,
                         const unsigned char tweak0[16], const unsigned char *input, unsigned char *output);
 
+/* AES-GCM (NIST SP 800-38D), written from the standard (the reference has no
+ * authenticated mode).  The host GHASH is the tests' oracle and hashes AAD
+ * and IVs for the device calls; it is table driven but no fast path. */
+#define POLARSSL_ERR_GCM_AUTH_FAILED -0x0012
+#define AES_GCM_MAX_BYTES ((((uint64_t)1) << 36) - 32) /* plaintext bytes of one message */
+typedef struct {
+    aes_context enc;          /* K, an encryption schedule (GCM never decrypts a block) */
+    unsigned char h[16];      /* H = E_K(0^128) */
+    uint64_t tab[32][16][2];  /* tab[p][n] = (nibble n at nibble position p) . H, as 16 memory-order bytes */
+} aes_gcm_context;
+int aes_gcm_setkey(aes_gcm_context *ctx, const unsigned char *key, unsigned int keybits);
+/* GHASH under an H given directly (ctx->enc is left alone) */
+void aes_gcm_set_h(aes_gcm_context *ctx, const unsigned char h[16]);
+/* z = x . y in GF(2^128), GCM's bit order; a bit loop, for constants */
+void aes_gf128_mul(unsigned char z[16], const unsigned char x[16], const unsigned char y[16]);
+/* y = GHASH_H continued from y over len bytes, the last partial block zero-padded */
+void aes_ghash(const aes_gcm_context *ctx, unsigned char y[16], const unsigned char *data, size_t len);
+/* J0: IV || 0^31 || 1 for 12-byte IVs, else GHASH(IV padded || 0^64 || [8 iv_len]_64) */
+void aes_gcm_j0(const aes_gcm_context *ctx, const unsigned char *iv, size_t iv_len, unsigned char j0[16]);
+/* GCM's counter mode: bytes 12..15 of ctr increment big-endian and wrap at
+ * 2^32 without carry; ctr is left at the next block's value */
+int aes_crypt_ctr32(aes_gcm_context *ctx, size_t length, unsigned char ctr[16], const unsigned char *input,
+                    unsigned char *output);
+/* mode AES_ENCRYPT / AES_DECRYPT; tag: the COMPUTED tag in both directions.
+ * iv_len >= 1, length <= AES_GCM_MAX_BYTES.  May run in place. */
+int aes_crypt_gcm(aes_gcm_context *ctx, int mode, size_t length, const unsigned char *iv, size_t iv_len,
+                  const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                  unsigned char tag[16]);
+/* decrypts and compares tag_len (4..16) tag bytes in constant time; on a
+ * mismatch output is zeroed and POLARSSL_ERR_GCM_AUTH_FAILED returned */
+int aes_gcm_auth_decrypt(aes_gcm_context *ctx, size_t length, const unsigned char *iv, size_t iv_len,
+                         const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
+                         const unsigned char *input, unsigned char *output);
+
 /* Monte-Carlo known-answer chains of the reference self-test
  * (aes-modes/aes.c:1084-1200): 10,000 chained operations from an all-zero
  * key / block / IV.  aes_monte_carlo writes the final block (CBC-enc: the last

@@ -210,6 +210,48 @@ int otc_xts_key_init(otc_xts_key *k, const uint8_t *key, int keybits /* 256 | 51
 int otc_aes_xts(const void *in, void *out, size_t unit_bytes, size_t nunits, const otc_xts_key *k,
                 const uint8_t tweak0[16], void *stream);
 
+/* AES-GCM (NIST SP 800-38D) of ONE message in device memory, 128/192/256-bit
+ * keys: nbytes is 0 .. 2^36 - 32 (any byte count), the IV any length >= 1
+ * (12 bytes: J0 = IV || 0^31 || 1; others through GHASH, as the standard
+ * says).  iv and aad are HOST memory -- AAD is for headers; hash large
+ * device-resident data with otc_ghash.  dir is OTC_DIR_ENCRYPT or
+ * OTC_DIR_DECRYPT; tag_dev is 16 bytes of device memory that receive the
+ * COMPUTED tag in both directions (comparing it with a received tag is the
+ * caller's: ops.gcm_decrypt does it with one readback).  Everything that does
+ * not depend on the data -- J0, E_K(J0), the AAD's hash state, the length
+ * block -- is computed on the host and travels by value, so the call does not
+ * synchronise and can be captured in a graph.  Stream order: encrypt: CTR32
+ * from inc32(J0), then GHASH over out; decrypt: GHASH over in, then CTR32 --
+ * in place works both ways; the hash ends in a one-wave kernel that writes
+ * the tag.
+ * nbytes == 0 launches only that.  Buffers are 16-byte aligned.  The hash's
+ * per-call tables and partials are stream-ordered allocations made BEFORE
+ * anything is launched: a failure (otc_fault_inject_alloc covers it) leaves
+ * out and tag_dev untouched.  impl chooses the CTR half's kernel, which is
+ * what otc_last_impl reports; the hash has one (csrc/hip/aes_gcm.hip). */
+typedef struct {
+    otc_aes_key enc; /* K's encryption schedule: GCM never runs the inverse cipher */
+    uint8_t h[16];   /* H = E_K(0^128) */
+} otc_gcm_key;
+int otc_gcm_key_init(otc_gcm_key *k, const uint8_t *key, int keybits);
+int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_gcm_key *k, int dir, const uint8_t *iv,
+                size_t iv_len, const uint8_t *aad, size_t aad_len, void *tag_dev, int impl, void *stream);
+/* GCM's counter mode: bytes 12..15 of ctr0 increment big-endian and wrap at
+ * 2^32, bytes 0..11 never change.  The CTR kernels of otc_aes_ctr, every
+ * impl: a call crosses the wrap at most once and is split there, on a block
+ * boundary, into two launches.  nbytes is at most 2^32 blocks. */
+int otc_aes_ctr32(const void *in, void *out, size_t nbytes, const otc_aes_key *k, const uint8_t ctr0[16], int impl,
+                  void *stream);
+/* y_dev[16] (device) = GHASH_h continued from y0 over nbytes (0 .. 2^36) of
+ * device data, 16-byte aligned, the last partial block zero-padded; h and y0
+ * are host memory.  Parallel over the whole chip. */
+int otc_ghash(const void *data, size_t nbytes, const uint8_t h[16], const uint8_t y0[16], void *y_dev, void *stream);
+/* Byte sizes of the pieces the GHASH kernel cuts its data into, smallest
+ * first (a pass of 64 lanes, a batch of passes, a wave's span, a workgroup's
+ * spans, a level-2 span, a level-3 span): lengths around them are where the
+ * kernel takes another path.  Writes up to max of them; returns the count. */
+int otc_ghash_spans(uint64_t *spans, int max);
+
 /* CFB128 decryption (parallel): P_i = C_i ^ E(C_{i-1}), C_{-1} = iv;
  * nbytes % 16 == 0; encryption key.  _impl: with a kernel choice (the plain
  * form is OTC_IMPL_AUTO: the T-table + bitsliced split from 2 GiB, the

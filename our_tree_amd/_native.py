@@ -73,6 +73,18 @@ class OtcXtsKey(ctypes.Structure):
     _fields_ = [("data", OtcAesKey), ("tweak", OtcAesKey)]
 
 
+class AesGcmContext(ctypes.Structure):
+    """Mirror of ``aes_gcm_context`` {enc, h, tab} (aes.h)."""
+
+    _fields_ = [("enc", AesContext), ("h", ctypes.c_uint8 * 16), ("tab", ctypes.c_uint64 * (32 * 16 * 2))]
+
+
+class OtcGcmKey(ctypes.Structure):
+    """Mirror of ``otc_gcm_key`` (otc.h): K's encryption schedule and H = E_K(0)."""
+
+    _fields_ = [("enc", OtcAesKey), ("h", ctypes.c_uint8 * 16)]
+
+
 class Arc4Context(ctypes.Structure):
     """Mirror of ``arc4_context`` {x, y, m[256]} (reference arc4.h:35-41)."""
 
@@ -147,6 +159,14 @@ def _declare_cpu(lib):
         "aes_xts_setkey_dec": (c_int, [P(AesXtsContext), c_u8p, ctypes.c_uint]),
         "aes_crypt_xts": (c_int, [P(AesXtsContext), c_int, c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_crypt_xts_units": (c_int, [P(AesXtsContext), c_int, c_sz, c_sz, c_u8p, c_u8p, c_u8p]),
+        "aes_gcm_setkey": (c_int, [P(AesGcmContext), c_u8p, ctypes.c_uint]),
+        "aes_gcm_set_h": (None, [P(AesGcmContext), c_u8p]),
+        "aes_gf128_mul": (None, [c_u8p, c_u8p, c_u8p]),
+        "aes_ghash": (None, [P(AesGcmContext), c_u8p, c_u8p, c_sz]),
+        "aes_gcm_j0": (None, [P(AesGcmContext), c_u8p, c_sz, c_u8p]),
+        "aes_crypt_ctr32": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_u8p, c_u8p]),
+        "aes_crypt_gcm": (c_int, [P(AesGcmContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p]),
+        "aes_gcm_auth_decrypt": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
         "arc4_setup": (None, [P(Arc4Context), c_u8p, ctypes.c_uint]),
         "arc4_prep": (c_int, [P(Arc4Context), c_sz, c_u8p]),
         "arc4_crypt": (c_int, [c_sz, c_u8p, c_u8p, c_u8p]),
@@ -196,6 +216,11 @@ def _declare_gpu(lib):
         "otc_last_impl": (c_int, []),
         "otc_xts_key_init": (c_int, [P(OtcXtsKey), c_u8p, c_int, c_int]),
         "otc_aes_xts": (c_int, [c_vp, c_vp, c_sz, c_sz, P(OtcXtsKey), c_u8p, c_vp]),
+        "otc_gcm_key_init": (c_int, [P(OtcGcmKey), c_u8p, c_int]),
+        "otc_aes_ctr32": (c_int, [c_vp, c_vp, c_sz, K, c_u8p, c_int, c_vp]),
+        "otc_ghash": (c_int, [c_vp, c_sz, c_u8p, c_u8p, c_vp, c_vp]),
+        "otc_aes_gcm": (c_int, [c_vp, c_vp, c_sz, P(OtcGcmKey), c_int, c_u8p, c_sz, c_u8p, c_sz, c_vp, c_int, c_vp]),
+        "otc_ghash_spans": (c_int, [P(c_u64), c_int]),
         "otc_split_stats": (None, [c_int]),
         "otc_split_fallback_reason": (ctypes.c_char_p, []),
         "otc_split_last_units": (c_int, [ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]),

@@ -160,3 +160,32 @@ class AESXTS:
         if isinstance(data, torch.Tensor):
             return ops.xts_decrypt(data, self._key, tweak0, unit_bytes, out=out)
         return cpu_ref.xts(self._key, tweak0, data, unit_bytes, decrypt=True)
+
+
+class AESGCM:
+    """AES-GCM (NIST SP 800-38D) with a 16, 24 or 32-byte ``key``: one message
+    per call, any IV length from 1 byte, ``aad`` as host bytes.  GPU tensors go
+    to the HIP kernels (CTR32 + the parallel GHASH; in place allowed), ``bytes``
+    to the C oracle.  ``encrypt`` returns ``(ciphertext, tag)``; ``decrypt``
+    takes the received tag (4 to 16 bytes) and raises ``ops.GcmTagError`` --
+    with the output zeroed -- when it does not match."""
+
+    def __init__(self, key: bytes):
+        key = bytes(key)
+        if len(key) not in (16, 24, 32):
+            raise ValueError("Invalid AES key size (16, 24 or 32 bytes).")
+        self._key = key
+
+    @property
+    def key_bits(self) -> int:
+        return len(self._key) * 8
+
+    def encrypt(self, data, iv: bytes, aad: bytes = b"", out=None, impl="auto"):
+        if isinstance(data, torch.Tensor):
+            return ops.gcm_encrypt(data, self._key, iv, aad, out=out, impl=impl)
+        return cpu_ref.gcm(self._key, iv, data, aad)
+
+    def decrypt(self, data, iv: bytes, tag, aad: bytes = b"", out=None, impl="auto"):
+        if isinstance(data, torch.Tensor):
+            return ops.gcm_decrypt(data, self._key, iv, tag, aad, out=out, impl=impl)
+        return cpu_ref.gcm_auth_decrypt(self._key, iv, data, tag, aad)

@@ -143,6 +143,102 @@ def xts(key: bytes, tweak0, data: bytes, unit_bytes: int | None = None, decrypt:
     return bytes(out)[: len(data)]
 
 
+GCM_MAX_BYTES = (1 << 36) - 32
+
+
+class GcmTagError(ValueError):
+    """The tag of an AES-GCM message did not match; the plaintext was zeroed."""
+
+
+def _gcm_ctx(key: bytes) -> _native.AesGcmContext:
+    ctx = _native.AesGcmContext()
+    key = bytes(key)
+    if _native.cpu_lib().aes_gcm_setkey(ctypes.byref(ctx), _native.as_u8p(key), len(key) * 8):
+        raise ValueError("invalid AES key length")
+    return ctx
+
+
+def _b16(v, name: str) -> bytes:
+    v = bytes(v)
+    if len(v) != 16:
+        raise ValueError(f"{name} must be 16 bytes")
+    return v
+
+
+def gf128_mul(x: bytes, y: bytes) -> bytes:
+    """x . y in GF(2^128) in GCM's bit order (the leftmost bit is x^0)."""
+    z = _buf(16)
+    _native.cpu_lib().aes_gf128_mul(z, _native.as_u8p(_b16(x, "x")), _native.as_u8p(_b16(y, "y")))
+    return bytes(z)
+
+
+def ghash(h: bytes, data: bytes, y0: bytes = bytes(16)) -> bytes:
+    """GHASH under ``h`` continued from ``y0`` over ``data``; the last partial
+    block is zero-padded (SP 800-38D)."""
+    ctx = _native.AesGcmContext()
+    lib = _native.cpu_lib()
+    lib.aes_gcm_set_h(ctypes.byref(ctx), _native.as_u8p(_b16(h, "h")))
+    y = (ctypes.c_uint8 * 16).from_buffer_copy(_b16(y0, "y0"))
+    data = bytes(data)
+    lib.aes_ghash(ctypes.byref(ctx), y, _native.as_u8p(data), len(data))
+    return bytes(y)
+
+
+def gcm_h(key: bytes) -> bytes:
+    """The hash subkey H = E_K(0^128)."""
+    return bytes(_gcm_ctx(key).h)
+
+
+def ctr32(key: bytes, ctr: bytes, data: bytes) -> bytes:
+    """GCM's counter mode: only bytes 12..15 of ``ctr`` increment (big-endian),
+    wrapping at 2**32 without carry into byte 11."""
+    ctx = _gcm_ctx(key)
+    c = (ctypes.c_uint8 * 16).from_buffer_copy(_b16(ctr, "ctr"))
+    data = bytes(data)
+    out = _buf(len(data))
+    _native.cpu_lib().aes_crypt_ctr32(ctypes.byref(ctx), len(data), c, _native.as_u8p(data), out)
+    return bytes(out)[: len(data)]
+
+
+def gcm(key: bytes, iv: bytes, data: bytes, aad: bytes = b"", decrypt: bool = False):
+    """AES-GCM (SP 800-38D) of one message: ``(out, tag)`` with the COMPUTED
+    16-byte tag in both directions.  Any IV length from 1 byte."""
+    ctx = _gcm_ctx(key)
+    iv, data, aad = bytes(iv), bytes(data), bytes(aad)
+    if not iv:
+        raise ValueError("the GCM IV must have at least 1 byte")
+    if len(data) > GCM_MAX_BYTES:
+        raise ValueError("a GCM message has at most 2**36 - 32 bytes")
+    out, tag = _buf(len(data)), _buf(16)
+    rc = _native.cpu_lib().aes_crypt_gcm(ctypes.byref(ctx), AES_DECRYPT if decrypt else AES_ENCRYPT, len(data),
+                                         _native.as_u8p(iv), len(iv), _native.as_u8p(aad), len(aad),
+                                         _native.as_u8p(data), out, tag)
+    if rc:
+        raise ValueError("invalid GCM lengths")
+    return bytes(out)[: len(data)], bytes(tag)
+
+
+def gcm_auth_decrypt(key: bytes, iv: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
+    """Authenticated decryption: compares 4..16 tag bytes in constant time and
+    raises GcmTagError (the C side zeroes its output) on a mismatch."""
+    ctx = _gcm_ctx(key)
+    iv, data, aad, tag = bytes(iv), bytes(data), bytes(aad), bytes(tag)
+    if not iv or not 4 <= len(tag) <= 16:
+        raise ValueError("GCM needs an IV of at least 1 byte and a tag of 4 to 16 bytes")
+    # not zero to begin with: err.output shows what the C side left on a mismatch
+    out = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(b"\xa5" * max(len(data), 1))
+    rc = _native.cpu_lib().aes_gcm_auth_decrypt(ctypes.byref(ctx), len(data), _native.as_u8p(iv), len(iv),
+                                                _native.as_u8p(aad), len(aad), _native.as_u8p(tag), len(tag),
+                                                _native.as_u8p(data), out)
+    if rc == -0x12:
+        err = GcmTagError("GCM tag mismatch")
+        err.output = bytes(out)[: len(data)]
+        raise err
+    if rc:
+        raise ValueError("invalid GCM lengths")
+    return bytes(out)[: len(data)]
+
+
 def serial_encrypt(mode: str, key: bytes, iv: bytes, data: bytes) -> bytes:
     """Exact single-stream CBC / CFB128 encryption on one core with AES-NI
     (the C oracle where AES-NI is absent).  This is the host path for the

@@ -2,7 +2,8 @@
 from .aes_ops import (IMPLS, CtrBatch, CtrStream, cbc_decrypt, cbc_decrypt_segments, cbc_encrypt_segments, cfb128_decrypt,
                       cfb128_decrypt_segments, cfb128_encrypt_segments,
                       ctr, ctr_batch, ctr_rfc3686, ecb_decrypt, ecb_encrypt, last_impl, pick_impl,
-                      split_fallback_reason, xts_decrypt, xts_encrypt)
+                      split_fallback_reason, xts_decrypt, xts_encrypt,
+                      GcmTagError, ctr32, gcm_decrypt, gcm_encrypt, ghash, ghash_spans)
 from .keys import expand_key
 from .stream_ops import checksum, clock_ghz, clock_probe, fill_random_, rc4_crypt_batch, rc4_multi, rc4_states, xor
 
@@ -11,4 +12,5 @@ __all__ = [
     "cbc_decrypt_segments", "cfb128_decrypt", "cfb128_encrypt_segments", "cfb128_decrypt_segments", "expand_key", "xor", "rc4_multi", "fill_random_", "checksum",
     "clock_probe", "clock_ghz", "pick_impl", "last_impl", "split_fallback_reason", "rc4_states", "rc4_crypt_batch",
     "xts_encrypt", "xts_decrypt",
+    "ctr32", "ghash", "ghash_spans", "gcm_encrypt", "gcm_decrypt", "GcmTagError",
 ]

@@ -11,10 +11,12 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import hmac
 
 import torch
 
 from .. import _native
+from ..models.cpu_ref import GcmTagError
 from .keys import DECRYPT, ENCRYPT, expand_key
 
 IMPLS = {"auto": 0, "ttable": 1, "bitslice": 2, "split": 3}  # otc.h OTC_IMPL_*
@@ -602,6 +604,103 @@ def xts_encrypt(x: torch.Tensor, key: bytes, tweak0, unit_bytes: int | None = No
 def xts_decrypt(x: torch.Tensor, key: bytes, tweak0, unit_bytes: int | None = None, out=None) -> torch.Tensor:
     """Inverse of ``xts_encrypt`` (as parallel, and also allowed in place)."""
     return _xts(x, key, tweak0, unit_bytes, out, True)
+
+
+GCM_MAX_BYTES = (1 << 36) - 32  # SP 800-38D: plaintext bytes of one message
+
+
+@functools.lru_cache(maxsize=64)
+def _gcm_key(key: bytes) -> _native.OtcGcmKey:
+    k = _native.OtcGcmKey()
+    if _lib().otc_gcm_key_init(ctypes.byref(k), _native.as_u8p(key), len(key) * 8):
+        raise ValueError(f"AES key must be 16, 24 or 32 bytes, got {len(key)}")
+    return k
+
+
+def ctr32(x: torch.Tensor, key: bytes, counter: bytes, out: torch.Tensor | None = None, impl="auto") -> torch.Tensor:
+    """GCM's counter mode: only bytes 12..15 of ``counter`` increment
+    (big-endian), wrapping at 2**32 with bytes 0..11 unchanged.  The CTR
+    kernels of ``ctr`` with every ``impl``; a call that crosses the wrap is
+    two launches.  Any byte length up to 2**32 blocks; may run in place."""
+    _check_dev(x, "x")
+    out = _out_like(x, out)
+    k = expand_key(key)
+    c = _b16(counter, "counter")
+    with torch.cuda.device(x.device):
+        rc = _run(x, out, lambda ip, op: _lib().otc_aes_ctr32(ip, op, _nbytes(x), ctypes.byref(k), c, _impl(impl),
+                                                             _stream(x)))
+    _native.check(rc, "otc_aes_ctr32")
+    return out
+
+
+def ghash(x: torch.Tensor, h: bytes, y0: bytes = bytes(16)) -> torch.Tensor:
+    """GHASH (SP 800-38D) under the hash subkey ``h``, continued from ``y0``,
+    over the bytes of ``x`` with the last partial block zero-padded: a 16-byte
+    uint8 tensor on ``x``'s device.  Parallel over the whole chip
+    (``csrc/hip/aes_gcm.hip``); asynchronous on the current stream."""
+    _check_dev(x, "x")
+    hb, yb = _b16(h, "h"), _b16(y0, "y0")
+    y = torch.empty(16, dtype=torch.uint8, device=x.device)
+    xb = _bytes(x)
+    if xb.data_ptr() % 16 and xb.numel():
+        xb = xb.clone()  # the kernel loads 16 bytes per lane
+    with torch.cuda.device(x.device):
+        rc = _lib().otc_ghash(xb.data_ptr(), xb.numel(), hb, yb, y.data_ptr(), _stream(x))
+    _native.check(rc, "otc_ghash")
+    return y
+
+
+def ghash_spans() -> list[int]:
+    """Byte sizes of the pieces the GHASH kernel cuts its data into, smallest
+    first (otc.h otc_ghash_spans): lengths around them take different paths."""
+    buf = (ctypes.c_uint64 * 16)()
+    n = _lib().otc_ghash_spans(buf, 16)
+    return [int(v) for v in buf[:n]]
+
+
+def _gcm(x: torch.Tensor, key: bytes, iv: bytes, aad: bytes, out, impl, decrypt: bool):
+    _check_dev(x, "x")
+    key, iv, aad = bytes(key), bytes(iv), bytes(aad)
+    if not iv:
+        raise ValueError("the GCM IV must have at least 1 byte")
+    n = _nbytes(x)
+    if n > GCM_MAX_BYTES:
+        raise ValueError("a GCM message has at most 2**36 - 32 bytes")
+    k = _gcm_key(key)
+    out = _out_like(x, out)
+    tag = torch.empty(16, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _run(x, out, lambda ip, op: _lib().otc_aes_gcm(
+            ip, op, n, ctypes.byref(k), DECRYPT if decrypt else ENCRYPT, _native.as_u8p(iv), len(iv),
+            _native.as_u8p(aad), len(aad), tag.data_ptr(), _impl(impl), _stream(x)))
+    _native.check(rc, "otc_aes_gcm")
+    return out, tag
+
+
+def gcm_encrypt(x: torch.Tensor, key: bytes, iv: bytes, aad: bytes = b"", out=None, impl="auto"):
+    """AES-GCM (SP 800-38D) encryption of one message: ``(out, tag)``, the tag
+    a 16-byte uint8 device tensor.  ``key`` is 16, 24 or 32 bytes, ``iv`` any
+    length from 1 byte (12 is the fast path), ``aad`` host bytes (headers;
+    hash large device data with ``ghash``).  Any byte length up to
+    2**36 - 32; may run in place; asynchronous -- nothing is read back.
+    ``impl`` chooses the CTR half's kernel (``last_impl()`` reports it)."""
+    return _gcm(x, key, iv, aad, out, impl, False)
+
+
+def gcm_decrypt(x: torch.Tensor, key: bytes, iv: bytes, tag, aad: bytes = b"", out=None, impl="auto") -> torch.Tensor:
+    """Authenticated AES-GCM decryption.  ``tag`` is the received tag, 4 to 16
+    bytes (bytes, or a uint8 tensor); the computed tag is read back -- 16
+    bytes, the call's only synchronisation -- and compared in constant time.
+    On a mismatch ``out`` is zeroed and ``GcmTagError`` (a ``ValueError``)
+    raised.  May run in place."""
+    tag = bytes(tag.cpu().numpy().tobytes()) if isinstance(tag, torch.Tensor) else bytes(tag)
+    if not 4 <= len(tag) <= 16:
+        raise ValueError("a GCM tag has 4 to 16 bytes")
+    out, t = _gcm(x, key, iv, aad, out, impl, True)
+    if not hmac.compare_digest(t.cpu().numpy().tobytes()[: len(tag)], tag):
+        out.zero_()
+        raise GcmTagError("GCM tag mismatch: the output was zeroed")
+    return out
 
 
 def _seg_call(fn_name: str, x: torch.Tensor, key: bytes, iv0: bytes, segment_bytes: int, out, inplace_ok: bool,
