@@ -657,6 +657,194 @@ extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_g
     return OTC_OK;
 }
 
+/* ---- batched GCM: many records, own IVs, one tag array --------------------- */
+extern "C" int otc_gcm_batch_spans(uint64_t *spans, int max)
+{
+    uint64_t none;
+    return otc_impl::gcm_batch_spans(spans ? spans : &none, spans ? max : 0);
+}
+
+extern "C" size_t otc_gcm_batch_table_bytes(void) { return otc_impl::gcm_batch_table_bytes(); }
+
+extern "C" size_t otc_gcm_batch_ws_bytes(size_t nmsg) { return nmsg * 32; /* J0[], then E_K(J0)[] */ }
+
+extern "C" int otc_gcm_batch_tables(const otc_gcm_key *k, void *tab_dev, void *stream)
+{
+    Range rg("otc_gcm_batch_tables");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (!tab_dev || ((uintptr_t)tab_dev & 15u))
+        return set_err(OTC_ERR_ARG, "gcm_batch: the tables must be 16-byte aligned device memory");
+    const hipError_t e = otc_impl::gcm_batch_tables(k->h, tab_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gcm_batch tables launch");
+    return OTC_OK;
+}
+
+extern "C" int64_t otc_gcm_batch_plan(const otc_gcm_msg *msgs, size_t nmsg, int tile_blocks, otc_ctr_msg *ctr_msgs,
+                                      uint32_t *tile_msg, uint64_t *tile_first)
+{
+    if (tile_blocks != 64 && tile_blocks != 128 && tile_blocks != 256)
+        return set_err(OTC_ERR_ARG, "gcm_batch: tile_blocks must be 64, 128 or 256");
+    if (nmsg == 0) return 0;
+    if (!msgs) return set_err(OTC_ERR_ARG, "gcm_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "gcm_batch: record " + std::to_string(m) + ": " + what);
+    };
+    struct Iv {
+        uint64_t lo, hi;
+        size_t m;
+    };
+    std::vector<Iv> outs; /* the non-empty outputs, to find records that overlap */
+    for (size_t m = 0; m < nmsg; ++m) {
+        const otc_gcm_msg &d = msgs[m];
+        /* at most 65536 blocks: the counter's low 32 bits, started at 2, never wrap */
+        if (d.nbytes > OTC_GCM_BATCH_MAX_BYTES) return bad(m, "more than 1 MiB of data (use otc_aes_gcm)");
+        if (d.aad_bytes > OTC_GCM_BATCH_MAX_AAD) return bad(m, "more than 64 KiB of AAD");
+        if (d.aad_bytes && !d.aad) return bad(m, "null aad");
+        if (!d.nbytes) continue;
+        if (!d.in || !d.out) return bad(m, "null buffer");
+        if ((d.in | d.out) & 15u) return bad(m, "data buffers must be 16-byte aligned");
+        if (d.in != d.out && d.in < d.out + d.nbytes && d.out < d.in + d.nbytes)
+            return bad(m, "input and output overlap partially");
+        outs.push_back({d.out, d.out + d.nbytes, m});
+    }
+    std::sort(outs.begin(), outs.end(), [](const Iv &a, const Iv &b) { return a.lo < b.lo; });
+    for (size_t i = 1; i < outs.size(); ++i)
+        if (outs[i].lo < outs[i - 1].hi) return bad(outs[i].m, "its output overlaps another record's");
+    for (size_t m = 0; m < nmsg; ++m) { /* no record reads what another writes */
+        const otc_gcm_msg &d = msgs[m];
+        if (!d.nbytes) continue;
+        auto it = std::upper_bound(outs.begin(), outs.end(), d.in,
+                                   [](uint64_t a, const Iv &o) { return a < o.hi; }); /* first output ending past in */
+        for (; it != outs.end() && it->lo < d.in + d.nbytes; ++it)
+            if (it->m != m) return bad(m, "its input overlaps another record's output");
+    }
+    for (size_t m = 0; m < nmsg; ++m) { /* an encryption writes every output before the hash reads the AADs */
+        const otc_gcm_msg &d = msgs[m];
+        if (!d.aad_bytes) continue;
+        auto it = std::upper_bound(outs.begin(), outs.end(), d.aad, [](uint64_t a, const Iv &o) { return a < o.hi; });
+        if (it != outs.end() && it->lo < d.aad + d.aad_bytes) return bad(m, "its AAD overlaps a record's output");
+    }
+    const uint64_t tile_bytes = 16ull * (uint64_t)tile_blocks;
+    uint64_t t = 0;
+    for (size_t m = 0; m < nmsg; ++m) {
+        const uint64_t nt = (msgs[m].nbytes + tile_bytes - 1) / tile_bytes;
+        if (ctr_msgs) ctr_msgs[m] = otc_ctr_msg{msgs[m].in, msgs[m].out, msgs[m].nbytes, 0, 0, 0, 0};
+        if (tile_first) tile_first[m] = t;
+        if (tile_msg)
+            for (uint64_t k = 0; k < nt; ++k) tile_msg[t + k] = (uint32_t)m;
+        t += nt;
+    }
+    return (int64_t)t;
+}
+
+/* 16 lanes per record for short records, 64 for long ones: measured on
+ * uniform batches, 16 wins at 1, 4 and 8 KiB records (x3.4, x1.8, x1.2), 64 at
+ * 16 KiB (x1.3); a mean of 768 hashed blocks (12 KiB), between the last two,
+ * is where the choice changes -- nothing between them was measured.  SUPPOSED,
+ * not measured: a group of records waits for the serial chain of its longest,
+ * nb / lanes multiplications, so one record above 4096 blocks also takes 64;
+ * no batch of mixed sizes has been timed (aes_gcm_batch.hip, docs/PERF.md
+ * "Batched AES-GCM"). */
+extern "C" int otc_gcm_batch_lanes(const otc_gcm_msg *msgs, size_t nmsg)
+{
+    uint64_t total = 0;
+    for (size_t m = 0; msgs && m < nmsg; ++m) {
+        const uint64_t nb = (msgs[m].aad_bytes + 15) / 16 + (msgs[m].nbytes + 15) / 16 + 1;
+        if (nb > 4096) return otc_impl::GB_LANES_LONG;
+        total += nb;
+    }
+    return nmsg && total / nmsg > 768 ? otc_impl::GB_LANES_LONG : otc_impl::GB_LANES_SHORT;
+}
+
+/* what otc_ghash_batch and otc_aes_gcm_batch check alike */
+static int gcm_batch_common(const otc_gcm_msg *msgs_dev, const void *tab_dev, const void *out16, const char *out_name,
+                            int &lanes)
+{
+    if (lanes == 0) lanes = otc_impl::GB_LANES_LONG;
+    if (lanes != otc_impl::GB_LANES_SHORT && lanes != otc_impl::GB_LANES_LONG)
+        return set_err(OTC_ERR_ARG, "gcm_batch: lanes must be 16 or 64 (0: 64)");
+    if (!msgs_dev || !tab_dev || !out16) return set_err(OTC_ERR_ARG, "gcm_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "gcm_batch: misaligned descriptor array");
+    if ((uintptr_t)tab_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_batch: the tables must be 16-byte aligned");
+    if ((uintptr_t)out16 & 15u) return set_err(OTC_ERR_ARG, std::string("gcm_batch: ") + out_name + " must be 16-byte aligned");
+    return OTC_OK;
+}
+
+extern "C" int otc_ghash_batch(const otc_gcm_msg *msgs_dev, size_t nmsg, const void *tab_dev, void *s_dev, int lanes,
+                               void *stream)
+{
+    Range rg("otc_ghash_batch");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = gcm_batch_common(msgs_dev, tab_dev, s_dev, "the hash array", lanes)) return r;
+    const hipError_t e = otc_impl::ghash_batch_run(msgs_dev, nmsg, tab_dev, s_dev, nullptr, nullptr, 16, nullptr, false,
+                                                   lanes, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "ghash_batch launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_gcm_batch(const otc_gcm_msg *msgs_dev, otc_ctr_msg *ctr_msgs_dev, const uint32_t *tile_msg_dev,
+                                 const uint64_t *tile_first_dev, uint64_t ntiles, int tile_blocks, size_t nmsg,
+                                 const otc_gcm_key *k, const otc_aes_key *key_dev, const void *tab_dev, int dir,
+                                 const uint8_t *ivs_dev, void *tags_dev, const uint8_t *expect_dev, int tag_bytes,
+                                 uint8_t *ok_dev, void *ws_dev, int lanes, void *stream)
+{
+    Range rg("otc_aes_gcm_batch");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (tile_blocks != 64 && tile_blocks != 128 && tile_blocks != 256)
+        return set_err(OTC_ERR_ARG, "gcm_batch: tile_blocks must be 64, 128 or 256");
+    if (tag_bytes < 4 || tag_bytes > 16) return set_err(OTC_ERR_ARG, "gcm_batch: a tag has 4 to 16 bytes");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = gcm_batch_common(msgs_dev, tab_dev, tags_dev, "the tag array", lanes)) return r;
+    if (!ctr_msgs_dev || !key_dev || !ws_dev) return set_err(OTC_ERR_ARG, "gcm_batch: null array");
+    if (ntiles && (!tile_msg_dev || !tile_first_dev)) return set_err(OTC_ERR_ARG, "gcm_batch: null tile map");
+    if ((((uintptr_t)ctr_msgs_dev) | ((uintptr_t)key_dev) | ((uintptr_t)tile_first_dev)) & 7u ||
+        ((uintptr_t)tile_msg_dev & 3u))
+        return set_err(OTC_ERR_ARG, "gcm_batch: misaligned descriptor arrays");
+    if ((uintptr_t)ws_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_batch: the workspace must be 16-byte aligned");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "gcm_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * (size_t)tag_bytes;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * 16 && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "gcm_batch: the expected tags overlap the computed tags or the verdicts");
+    }
+    if (!ivs_dev) return set_err(OTC_ERR_ARG, "gcm_batch: null IVs");
+    hipStream_t st = (hipStream_t)stream;
+    g_last_impl = OTC_IMPL_TTABLE;
+    uint8_t *j0 = (uint8_t *)ws_dev, *ekj0 = j0 + nmsg * 16;
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+
+    hipError_t e = otc_impl::gcm_batch_prep(ivs_dev, nmsg, ctr_msgs_dev, j0, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_batch prep launch");
+    /* E_K(J0[]): the grid T-table kernel, ECB over nmsg blocks */
+    const Job job{otc_impl::JOB_ECB_ENC, j0, ekj0, nmsg, &k->enc, nullptr, 0};
+    if ((e = otc_impl::tt_run(job, nmsg, st)) != hipSuccess) return hip_fail(e, "gcm_batch E_K(J0) launch");
+    /* the CTR half: the batched kernel's static split (the claimed form
+     * allocates its counter) */
+    auto ctr = [&] {
+        return ntiles ? otc_impl::tt_ctr_batch(ctr_msgs_dev, key_dev, tile_msg_dev, tile_first_dev, ntiles, tile_blocks,
+                                               k->enc.nr, st, nullptr)
+                      : hipSuccess;
+    };
+    if (enc && (e = ctr()) != hipSuccess) return hip_fail(e, "gcm_batch ctr launch");
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    e = otc_impl::ghash_batch_run(msgs_dev, nmsg, tab_dev, tags_dev, ekj0, enc ? nullptr : expect_dev, tag_bytes,
+                                  enc ? nullptr : ok_dev, enc, lanes, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_batch hash launch");
+    if (!enc) {
+        if ((e = ctr()) != hipSuccess) return hip_fail(e, "gcm_batch ctr launch");
+        if ((e = otc_impl::gcm_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+            return hip_fail(e, "gcm_batch wipe launch");
+    }
+    return OTC_OK;
+}
+
 extern "C" int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream)
 {
     Range rg("otc_xor");

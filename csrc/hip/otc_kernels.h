@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_gcm.hip, aes_bs.hip, stream_ops.hip), declared once: included by their callers
+ * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, stream_ops.hip), declared once: included by their callers
  * (engine.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
  * of the public C API (otc.h).
@@ -104,6 +104,24 @@ hipError_t ghash_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws);
  * behind its kernels, also when it fails. */
 hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], const uint8_t y0[16],
                      const uint8_t *lenblock, const uint8_t *ekj0, void *out16, void *ws, hipStream_t st);
+
+/* ---- aes_gcm_batch.hip --------------------------------------------------- */
+/* lanes per record of the batched hash kernel's two forms */
+constexpr int GB_LANES_SHORT = 16, GB_LANES_LONG = 64;
+/* the batched hash kernel's boundaries in hashed blocks, smallest first */
+int gcm_batch_spans(uint64_t *spans, int max);
+size_t gcm_batch_table_bytes();
+/* the per-key table image (H^16, H^64, H) from h, and the kernels' LDS opt-in */
+hipError_t gcm_batch_tables(const uint8_t h[16], void *tab, hipStream_t st);
+/* out16[m] = GHASH of record m (its `out` data with hash_out, else its `in`),
+ * XORed with ekj0[m] if given; with ok, ok[m] = the first tag_bytes bytes equal
+ * expect[m].  lanes: GB_LANES_SHORT or GB_LANES_LONG per record */
+hipError_t ghash_batch_run(const otc_gcm_msg *msgs, uint64_t nmsg, const void *tab, void *out16, const void *ekj0,
+                           const uint8_t *expect, int tag_bytes, uint8_t *ok, bool hash_out, int lanes, hipStream_t st);
+/* ivs (nmsg x 12) -> the counters of ctr_msgs (IV || 00000002) and j0 (IV || 00000001) */
+hipError_t gcm_batch_prep(const uint8_t *ivs, uint64_t nmsg, otc_ctr_msg *ctr_msgs, void *j0, hipStream_t st);
+/* zero the output of every record with ok[m] == 0 */
+hipError_t gcm_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st);
 
 /* ---- aes_bs.hip ---------------------------------------------------------- */
 hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,

@@ -303,6 +303,92 @@ uint64_t otc_ctr_batch_plan(const otc_ctr_msg *msgs, size_t nmsg, int tile_block
 int otc_aes_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const uint32_t *tile_msg,
                       const uint64_t *tile_first, uint64_t ntiles, int tile_blocks, int nr, void *stream);
 
+/* ---- batched AES-GCM ------------------------------------------------------
+ * Many records under ONE key, each with its own 12-byte IV, its own AAD and
+ * its own 16-byte tag: record m is SP 800-38D GCM under (key, iv[m], aad[m]).
+ * The shape of TLS records, ESP / QUIC packets and sealed sectors, where
+ * otc_aes_gcm's per-call cost (an allocation, 384 KiB of tables, one launch per
+ * level) is all there is.  One key per batch is a decision: the positional
+ * hash tables are 64 KiB per constant and cannot be held per record.
+ *
+ * Limits (the planner checks them on host copies of the descriptors): data
+ * 0 .. OTC_GCM_BATCH_MAX_BYTES per record, any byte count -- larger messages
+ * belong to otc_aes_gcm; AAD 0 .. OTC_GCM_BATCH_MAX_AAD, device memory, any
+ * alignment; data buffers 16-byte aligned; in == out allowed per record;
+ * distinct records must not overlap, and no AAD may overlap any record's
+ * output (an encryption writes the outputs before it hashes the AADs).  A record of 0 bytes is valid, with AAD
+ * (GMAC) or without.  Only 12-byte IVs: other lengths need a hash to form J0.
+ * The cap makes a record at most 65536 blocks, so from IV || 00000002 the low
+ * 32 counter bits never wrap and the 128-bit add of the batched CTR kernel IS
+ * GCM's CTR32 here.
+ *
+ * The IVs are DEVICE data supplied to every run (n x 12 bytes): a replayed
+ * batch must bring new IVs, and IV uniqueness under a key is the caller's
+ * duty.  A run is one linear chain of launches on `stream` -- no allocation,
+ * no host synchronisation, no second stream -- so it can be captured in a graph:
+ *   encrypt: prep -> E_K(J0[]) -> CTR batch -> batched GHASH over out -> tags
+ *   decrypt: prep -> E_K(J0[]) -> batched GHASH over in -> tags, verdicts
+ *            -> CTR batch -> wipe
+ * prep writes IV || 00000002 into the otc_ctr_msg descriptors and J0 = IV ||
+ * 00000001 into the workspace.  On decryption the first tag_bytes (4 .. 16)
+ * bytes of every computed tag are compared on the device with expect_dev
+ * (n x tag_bytes; OR of the XORs, no early exit), ok_dev[m] becomes 1 or 0,
+ * and after the CTR pass the output of every record with ok_dev[m] == 0 is
+ * zeroed (in place: the ciphertext with it), and so is its row of tags_dev:
+ * the computed tag of a forged record is the valid tag of that forgery and is
+ * not handed out.  expect_dev must not overlap tags_dev or ok_dev (rejected).  otc_last_impl: OTC_IMPL_TTABLE. */
+#define OTC_GCM_BATCH_MAX_BYTES (1u << 20)
+#define OTC_GCM_BATCH_MAX_AAD (1u << 16)
+typedef struct {
+    uint64_t in;        /* device addresses */
+    uint64_t out;
+    uint64_t nbytes;
+    uint64_t aad;
+    uint64_t aad_bytes;
+    uint64_t reserved;
+} otc_gcm_msg;
+
+/* The per-key hash tables (H^16, H^64 and H, 64 KiB each) in tab_dev, 16-byte
+ * aligned device memory of otc_gcm_batch_table_bytes(): once per key. */
+size_t otc_gcm_batch_table_bytes(void);
+int otc_gcm_batch_tables(const otc_gcm_key *k, void *tab_dev, void *stream);
+/* Host planner over HOST copies of the descriptors: checks the caps, the
+ * alignment, partial overlap of a record's in and out, overlap between
+ * records and of an AAD with any output; fills the CTR half's descriptors (counters left zero: prep writes
+ * them), tile map and tile_first -- any of the three may be NULL to only
+ * count.  Returns the number of tiles (records of 0 bytes have none), or
+ * OTC_ERR_ARG with a message. */
+int64_t otc_gcm_batch_plan(const otc_gcm_msg *msgs, size_t nmsg, int tile_blocks, otc_ctr_msg *ctr_msgs,
+                           uint32_t *tile_msg, uint64_t *tile_first);
+/* the caller-owned workspace of a run: J0[] and E_K(J0)[], 16-byte aligned */
+size_t otc_gcm_batch_ws_bytes(size_t nmsg);
+/* How many lanes hash one record: the kernel has a 16-lane form (four records
+ * per wave, a short fold: short records) and a 64-lane form (one wave per
+ * record: long ones).  Both compute the same; the choice is speed only.  From
+ * HOST copies of the descriptors: 64 when the records hash more than 768 blocks
+ * (12 KiB) on average or one of them more than 4096 (64 KiB), else 16. */
+int otc_gcm_batch_lanes(const otc_gcm_msg *msgs, size_t nmsg);
+/* The hash by itself: s_dev[m] (nmsg x 16, 16-byte aligned) = GHASH_H of
+ * record m's AAD, `in` data and length block.  lanes: 16 or 64 (0: 64). */
+int otc_ghash_batch(const otc_gcm_msg *msgs_dev, size_t nmsg, const void *tab_dev, void *s_dev, int lanes,
+                    void *stream);
+/* tags_dev: nmsg x 16, 16-byte aligned, the COMPUTED tags in both directions
+ * (decryption: zero for the records that fail);
+ * expect_dev / ok_dev: decryption only.  key_dev: a device copy of k->enc, 8-byte
+ * aligned (the keys[] array of the batched CTR kernel, which reads round keys
+ * from memory; the call itself copies nothing).  lanes: as otc_ghash_batch.
+ * nmsg == 0 launches nothing. */
+int otc_aes_gcm_batch(const otc_gcm_msg *msgs_dev, otc_ctr_msg *ctr_msgs_dev, const uint32_t *tile_msg_dev,
+                      const uint64_t *tile_first_dev, uint64_t ntiles, int tile_blocks, size_t nmsg,
+                      const otc_gcm_key *k, const otc_aes_key *key_dev, const void *tab_dev, int dir,
+                      const uint8_t *ivs_dev, void *tags_dev, const uint8_t *expect_dev, int tag_bytes, uint8_t *ok_dev,
+                      void *ws_dev, int lanes, void *stream);
+/* The batched hash kernel's own boundaries in HASHED BLOCKS (AAD, data and
+ * length block together), smallest first: a pass of the 16-lane form (16), its
+ * batch of passes which is also a pass of the 64-lane form (64), a batch of
+ * those (256).  Writes up to max of them; returns the count. */
+int otc_gcm_batch_spans(uint64_t *spans, int max);
+
 /* out = a ^ b (the device arc4_crypt combiner). */
 int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream);
 

@@ -221,6 +221,15 @@ def _declare_gpu(lib):
         "otc_ghash": (c_int, [c_vp, c_sz, c_u8p, c_u8p, c_vp, c_vp]),
         "otc_aes_gcm": (c_int, [c_vp, c_vp, c_sz, P(OtcGcmKey), c_int, c_u8p, c_sz, c_u8p, c_sz, c_vp, c_int, c_vp]),
         "otc_ghash_spans": (c_int, [P(c_u64), c_int]),
+        "otc_gcm_batch_spans": (c_int, [P(c_u64), c_int]),
+        "otc_gcm_batch_table_bytes": (c_sz, []),
+        "otc_gcm_batch_ws_bytes": (c_sz, [c_sz]),
+        "otc_gcm_batch_tables": (c_int, [P(OtcGcmKey), c_vp, c_vp]),
+        "otc_gcm_batch_plan": (ctypes.c_int64, [c_vp, c_sz, c_int, c_vp, c_vp, c_vp]),
+        "otc_gcm_batch_lanes": (c_int, [c_vp, c_sz]),
+        "otc_ghash_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
+        "otc_aes_gcm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u64, c_int, c_sz, P(OtcGcmKey), c_vp, c_vp, c_int,
+                                      c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
         "otc_split_stats": (None, [c_int]),
         "otc_split_fallback_reason": (ctypes.c_char_p, []),
         "otc_split_last_units": (c_int, [ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]),

@@ -189,3 +189,15 @@ class AESGCM:
         if isinstance(data, torch.Tensor):
             return ops.gcm_decrypt(data, self._key, iv, tag, aad, out=out, impl=impl)
         return cpu_ref.gcm_auth_decrypt(self._key, iv, data, tag, aad)
+
+    def encrypt_batch(self, xs, ivs, aads=None, outs=None):
+        """Many records in one run (``ops.GcmBatch``): GPU tensors ``xs``, a
+        device uint8 [n, 12] tensor of IVs, never reused under this key;
+        ``(outs, tags)`` with the tags a device uint8 [n, 16] tensor."""
+        return ops.gcm_encrypt_batch(xs, self._key, ivs, aads=aads, outs=outs)
+
+    def decrypt_batch(self, xs, ivs, tags, aads=None, outs=None):
+        """``(outs, ok)``: ``ok`` a device bool [n] tensor; the output of every
+        record whose tag (device uint8 [n, 4..16]) does not match is zeroed.
+        Nothing is read back and nothing raised."""
+        return ops.gcm_decrypt_batch(xs, self._key, ivs, tags, aads=aads, outs=outs)

@@ -3,7 +3,8 @@ from .aes_ops import (IMPLS, CtrBatch, CtrStream, cbc_decrypt, cbc_decrypt_segme
                       cfb128_decrypt_segments, cfb128_encrypt_segments,
                       ctr, ctr_batch, ctr_rfc3686, ecb_decrypt, ecb_encrypt, last_impl, pick_impl,
                       split_fallback_reason, xts_decrypt, xts_encrypt,
-                      GcmTagError, ctr32, gcm_decrypt, gcm_encrypt, ghash, ghash_spans)
+                      GcmTagError, ctr32, gcm_decrypt, gcm_encrypt, ghash, ghash_spans,
+                      GcmBatch, gcm_batch_spans, gcm_decrypt_batch, gcm_encrypt_batch, ghash_batch)
 from .keys import expand_key
 from .stream_ops import checksum, clock_ghz, clock_probe, fill_random_, rc4_crypt_batch, rc4_multi, rc4_states, xor
 
@@ -13,4 +14,5 @@ __all__ = [
     "clock_probe", "clock_ghz", "pick_impl", "last_impl", "split_fallback_reason", "rc4_states", "rc4_crypt_batch",
     "xts_encrypt", "xts_decrypt",
     "ctr32", "ghash", "ghash_spans", "gcm_encrypt", "gcm_decrypt", "GcmTagError",
+    "GcmBatch", "gcm_encrypt_batch", "gcm_decrypt_batch", "ghash_batch", "gcm_batch_spans",
 ]

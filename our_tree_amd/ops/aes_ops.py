@@ -703,6 +703,363 @@ def gcm_decrypt(x: torch.Tensor, key: bytes, iv: bytes, tag, aad: bytes = b"", o
     return out
 
 
+GCM_BATCH_MAX_BYTES = 1 << 20  # otc.h OTC_GCM_BATCH_MAX_BYTES
+GCM_BATCH_MAX_AAD = 1 << 16  # otc.h OTC_GCM_BATCH_MAX_AAD
+
+
+class GcmBatch:
+    """A planned batch of AES-GCM records under ONE key -- own buffers, own
+    12-byte IV, own AAD and own 16-byte tag each (``otc_aes_gcm_batch``).
+    Record ``m`` is SP 800-38D GCM under ``(key, ivs[m], aads[m])``.
+
+    The serving shape: TLS records, ESP / QUIC packets, sealed sectors.  One
+    ``gcm_encrypt`` per record pays an allocation, 384 KiB of hash tables and
+    a launch per level each time; here planning -- validation, descriptors,
+    the CTR half's tile map, the key schedule, the per-key hash tables, the
+    workspace, one pinned upload -- happens once in the constructor, and
+    ``encrypt`` / ``decrypt`` only launch one linear chain of kernels on one
+    stream: no allocation, no host synchronisation, capturable in a
+    ``torch.cuda.CUDAGraph``.  They can be replayed with new data in the same
+    buffers.
+
+    **IV uniqueness under a key is the caller's duty, and a replay must bring
+    new IVs**: that is why the IVs are no part of the plan but a device
+    ``uint8 [n, 12]`` tensor handed to every run (a captured graph reads the
+    tensor's contents at replay: change them in place).  Only 12-byte IVs.
+
+    xs / outs: GPU tensors (contiguous, 16-byte aligned; ``outs[i] is xs[i]``
+    for in place), 0 .. 1 MiB each, any byte count -- larger messages belong
+    to ``gcm_encrypt``.  Distinct records must not overlap.  aads: ``None``, a
+    device ``uint8 [n, A]`` tensor (row m is record m's AAD), or a list with
+    one entry per record: a device tensor or host bytes (uploaded once with
+    the plan), 0 .. 64 KiB each, any alignment; no AAD may overlap any
+    record's output (an encryption writes the outputs before it hashes).  A
+    record of 0 bytes is valid, with AAD (GMAC) or without.  One key per batch: the hash tables are 64 KiB
+    per constant and cannot be held per record.  tag_bytes: how many bytes of a
+    tag ``decrypt`` compares (4 .. 16).  lanes: 16 or 64 lanes of the hash
+    kernel per record (default: 16 for records up to 12 KiB on average and no
+    record above 64 KiB, else 64; the result is the same, only the speed
+    differs).
+
+    ``tags`` and ``ok`` are the batch's own tensors, overwritten by the next
+    run; ``decrypt`` therefore refuses ``self.tags`` as the expected tags."""
+
+    def __init__(self, xs, key: bytes, outs=None, aads=None, tag_bytes: int = 16, tile_blocks=None, lanes=None):
+        import numpy as np
+
+        self._init_common(key, tag_bytes, lanes)
+        xs = list(xs)
+        n = len(xs)
+        if outs is None:
+            outs = [torch.empty_like(x) for x in xs]
+        outs = list(outs)
+        if len(outs) != n:
+            raise ValueError("one output per record")
+        self.outs = outs
+        self._keep = [xs]
+        self.device = xs[0].device if n else None
+        desc = np.zeros((n, 6), dtype=np.uint64)  # in, out, nbytes, aad, aad_bytes, reserved
+        for i, (x, o) in enumerate(zip(xs, outs)):
+            _check_dev(x, f"xs[{i}]")
+            _check_dev(o, f"outs[{i}]")
+            if x.device != self.device or o.device != self.device:
+                raise ValueError("all records must be on one device")
+            nb = _nbytes(x)
+            if _nbytes(o) != nb:
+                raise ValueError(f"outs[{i}] must have the byte size of xs[{i}]")
+            if nb > GCM_BATCH_MAX_BYTES:
+                raise ValueError(f"record {i}: more than 1 MiB of data (use gcm_encrypt for large messages)")
+            desc[i, :3] = (x.data_ptr() if nb else 0, o.data_ptr() if nb else 0, nb)
+        self._set_aads(desc, aads)
+        self._build(desc, tile_blocks)
+
+    @classmethod
+    def packed(cls, buf: torch.Tensor, lengths, key: bytes, out: torch.Tensor | None = None, offsets=None, aad=None,
+               tag_bytes: int = 16, tile_blocks=None, lanes=None) -> "GcmBatch":
+        """Records packed in ONE device buffer, ``CtrBatch.packed``'s layout:
+        record i is ``buf[offsets[i] : offsets[i] + lengths[i]]`` (offsets
+        default to back-to-back 16-byte aligned slots) and lands at the same
+        offset of ``out`` (default: a new buffer; ``out is buf`` for in
+        place).  aad: ``None`` or a device ``uint8 [n, A]`` tensor.  Bytes of
+        ``out`` outside the records are not written.  The output is
+        ``self.out``."""
+        import numpy as np
+
+        self = cls.__new__(cls)
+        self._init_common(key, tag_bytes, lanes)
+        _check_dev(buf, "buf")
+        nb = _nbytes(buf)
+        lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        n = lens.size
+        if offsets is None:
+            offs = np.zeros(n, dtype=np.int64)
+            if n > 1:
+                offs[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
+        else:
+            offs = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        if offs.size != n:
+            raise ValueError("one offset per record")
+        if n and ((lens < 0).any() or (offs < 0).any() or (offs + lens > nb).any()):
+            raise ValueError("records must lie inside the buffer")
+        if n and (offs % 16).any():
+            raise ValueError("record offsets must be multiples of 16")
+        if n and (lens > GCM_BATCH_MAX_BYTES).any():
+            raise ValueError("a record has at most 1 MiB of data (use gcm_encrypt for large messages)")
+        out = _out_like(buf, out)
+        pi, po = buf.data_ptr(), out.data_ptr()
+        if (pi | po) % 16:
+            raise ValueError("buf / out must be 16-byte aligned")
+        if pi != po and pi < po + nb and po < pi + nb:
+            raise ValueError("buf and out overlap partially")
+        if out.device != buf.device:
+            raise ValueError("buf and out must be on one device")
+        self.out = out
+        self.outs = [out]
+        self._keep = [buf]
+        self.device = buf.device
+        desc = np.zeros((n, 6), dtype=np.uint64)
+        desc[:, 0] = np.uint64(pi) + offs.astype(np.uint64)
+        desc[:, 1] = np.uint64(po) + offs.astype(np.uint64)
+        desc[:, 2] = lens.astype(np.uint64)
+        if aad is not None and not isinstance(aad, torch.Tensor):
+            raise ValueError("aad must be a device uint8 [n, A] tensor")
+        self._set_aads(desc, aad)
+        self._build(desc, tile_blocks)
+        return self
+
+    def _init_common(self, key, tag_bytes, lanes):
+        if not isinstance(tag_bytes, int) or not 4 <= tag_bytes <= 16:
+            raise ValueError("a GCM tag has 4 to 16 bytes")
+        if lanes not in (None, 16, 64):
+            raise ValueError("lanes must be 16 or 64 (default: picked from the record sizes)")
+        self.tag_bytes = tag_bytes
+        self.lanes = lanes
+        self._k = _gcm_key(bytes(key))
+        self.n = 0
+        self.ntiles = 0
+        self.tags = self.ok = None
+
+    def _set_aads(self, desc, aads):
+        """Columns 3 and 4 of the descriptors; host AADs go to one device buffer."""
+        import numpy as np
+
+        n = desc.shape[0]
+        if aads is None or n == 0:
+            if isinstance(aads, (list, tuple)) and len(aads) != n:
+                raise ValueError("one AAD per record")
+            return
+        if isinstance(aads, torch.Tensor):
+            _check_dev(aads, "aads")
+            if aads.dtype != torch.uint8 or aads.dim() != 2 or aads.shape[0] != n:
+                raise ValueError(f"aads must be a uint8 [{n}, A] tensor")
+            if aads.device != self.device:
+                raise ValueError("aads must be on the records' device")
+            a = int(aads.shape[1])
+            if a > GCM_BATCH_MAX_AAD:
+                raise ValueError("a record has at most 64 KiB of AAD")
+            self._keep.append(aads)
+            if a:
+                desc[:, 3] = np.uint64(aads.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(a)
+                desc[:, 4] = a
+            return
+        aads = list(aads)
+        if len(aads) != n:
+            raise ValueError("one AAD per record")
+        host, at = [], 0
+        for i, a in enumerate(aads):
+            if isinstance(a, torch.Tensor):
+                _check_dev(a, f"aads[{i}]")
+                if a.device != self.device:
+                    raise ValueError("aads must be on the records' device")
+                na = _nbytes(a)
+                addr = a.data_ptr()
+            else:
+                a = b"" if a is None else bytes(a)
+                na, addr = len(a), None
+            if na > GCM_BATCH_MAX_AAD:
+                raise ValueError(f"record {i}: more than 64 KiB of AAD")
+            if na and addr is None:
+                host.append((i, at, a))
+                at += na
+            elif na:
+                desc[i, 3] = addr
+            desc[i, 4] = na
+        self._keep.append(aads)
+        if host:
+            blob = torch.frombuffer(bytearray(b"".join(a for _, _, a in host)), dtype=torch.uint8).pin_memory()
+            dev = blob.to(self.device, non_blocking=True)
+            self._keep.append((blob, dev))
+            for i, off, _ in host:
+                desc[i, 3] = dev.data_ptr() + off
+
+    def _build(self, desc, tile_blocks):
+        """Planner (validation + the CTR half's tile map) -> one pinned upload;
+        the key's hash tables; workspace, tags, verdicts."""
+        import numpy as np
+
+        n = desc.shape[0]
+        self.n = n
+        if tile_blocks is None:
+            tile_blocks = _pick_tile(desc[:, 2]) if n else 256
+        if tile_blocks not in BATCH_TILES:
+            raise ValueError(f"tile_blocks must be one of {BATCH_TILES}")
+        self.tile_blocks = tile_blocks
+        if n == 0:
+            return
+        lib = _lib()
+        desc = np.ascontiguousarray(desc)
+        ntiles = lib.otc_gcm_batch_plan(desc.ctypes.data, n, tile_blocks, None, None, None)
+        if ntiles < 0:
+            raise ValueError((lib.otc_last_error() or b"").decode())
+        ctr = np.zeros((n, 6), dtype=np.uint64)
+        first = np.zeros(n, dtype=np.uint64)
+        tmap = np.zeros(max(ntiles, 1), dtype=np.uint32)
+        if lib.otc_gcm_batch_plan(desc.ctypes.data, n, tile_blocks, ctr.ctypes.data, tmap.ctypes.data,
+                                  first.ctypes.data) != ntiles:
+            raise RuntimeError("otc_gcm_batch_plan: the two passes disagree")
+        parts, off = [], 0
+
+        def add(b: bytes) -> int:
+            nonlocal off
+            pad = (-off) % 16
+            if pad:
+                parts.append(bytes(pad))
+                off += pad
+            at = off
+            parts.append(b)
+            off += len(b)
+            return at
+
+        if self.lanes is None:
+            self.lanes = lib.otc_gcm_batch_lanes(desc.ctypes.data, n)
+        self._o_key = add(bytes(self._k.enc))  # otc_aes_key[1]: the CTR half reads round keys from memory
+        self._o_desc = add(desc.tobytes())
+        self._o_ctr = add(ctr.tobytes())
+        self._o_first = add(first.tobytes())
+        self._o_map = add(tmap.tobytes())
+        self.ntiles = int(ntiles)
+        dev = self.device
+        with torch.cuda.device(dev):
+            host = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).pin_memory()
+            self._plan = host.to(dev, non_blocking=True)
+            self._tab = torch.empty(lib.otc_gcm_batch_table_bytes(), dtype=torch.uint8, device=dev)
+            self._ws = torch.empty(lib.otc_gcm_batch_ws_bytes(n), dtype=torch.uint8, device=dev)
+            self.tags = torch.empty((n, 16), dtype=torch.uint8, device=dev)
+            self.ok = torch.zeros(n, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev)
+            _native.check(lib.otc_gcm_batch_tables(ctypes.byref(self._k), self._tab.data_ptr(),
+                                                   ctypes.c_void_p(st.cuda_stream)), "otc_gcm_batch_tables")
+            # planning may wait; the runs never do, on whatever stream (or capture) they go
+            st.synchronize()
+
+    def _check_ivs(self, ivs):
+        if not isinstance(ivs, torch.Tensor) or ivs.device.type != "cuda":
+            raise ValueError("ivs must be a GPU tensor, uint8 [n, 12]")
+        if ivs.dtype != torch.uint8 or ivs.dim() != 2 or not ivs.is_contiguous():
+            raise ValueError("ivs must be a contiguous uint8 [n, 12] tensor")
+        if ivs.shape[1] != 12:
+            raise ValueError(f"only 12-byte IVs are accepted (got {ivs.shape[1]} bytes): other lengths need a hash "
+                             "to form J0 -- use gcm_encrypt")
+        if ivs.shape[0] != self.n:
+            raise ValueError(f"one IV per record: ivs must be [{self.n}, 12]")
+        if self.n and ivs.device != self.device:
+            raise ValueError("ivs must be on the records' device")
+
+    def _launch(self, decrypt, ivs, expect, stream):
+        if self.n == 0:
+            return
+        st = stream or torch.cuda.current_stream(self.device)
+        base = self._plan.data_ptr()
+        with torch.cuda.device(self.device):
+            rc = _lib().otc_aes_gcm_batch(
+                base + self._o_desc, base + self._o_ctr, base + self._o_map, base + self._o_first, self.ntiles,
+                self.tile_blocks, self.n, ctypes.byref(self._k), base + self._o_key, self._tab.data_ptr(),
+                DECRYPT if decrypt else ENCRYPT, ivs.data_ptr(), self.tags.data_ptr(),
+                expect.data_ptr() if decrypt else None, self.tag_bytes, self.ok.data_ptr() if decrypt else None,
+                self._ws.data_ptr(), self.lanes, ctypes.c_void_p(st.cuda_stream))
+        _native.check(rc, "otc_aes_gcm_batch")
+
+    def _empty(self, shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=self.device or "cpu")
+
+    def encrypt(self, ivs: torch.Tensor, stream=None):
+        """Seal every record under ``ivs`` (device uint8 [n, 12]):
+        ``(outs, tags)``, the tags a device uint8 [n, 16] tensor.  Only
+        launches; every call must bring IVs never used under this key."""
+        self._check_ivs(ivs)
+        self._launch(False, ivs, None, stream)
+        return self.outs, (self.tags if self.n else self._empty((0, 16), torch.uint8))
+
+    def decrypt(self, ivs: torch.Tensor, tags: torch.Tensor, stream=None):
+        """Open every record: ``(outs, ok)`` with ``ok`` a device bool [n]
+        tensor.  tags: the received tags, device uint8 [n, tag_bytes].  The
+        comparison runs on the device; the output of every record whose tag
+        does not match is zeroed (in place: the ciphertext with it) and so is
+        its row of ``self.tags`` -- the computed tag of a forged record is the
+        valid tag of that forgery and is not handed out; the others are
+        unaffected.  Nothing is read back.  ``tags`` must not be (or overlap)
+        the batch's own ``self.tags``, which every run overwrites with what
+        it computes: pass a copy (``ValueError`` otherwise)."""
+        self._check_ivs(ivs)
+        if not isinstance(tags, torch.Tensor) or tags.device.type != "cuda":
+            raise ValueError(f"tags must be a GPU tensor, uint8 [n, {self.tag_bytes}]")
+        if tags.dtype != torch.uint8 or tags.dim() != 2 or not tags.is_contiguous() or \
+                tuple(tags.shape) != (self.n, self.tag_bytes):
+            raise ValueError(f"tags must be a contiguous uint8 [{self.n}, {self.tag_bytes}] tensor")
+        if self.n and tags.device != self.device:
+            raise ValueError("tags must be on the records' device")
+        if self.n:
+            e0, e1 = tags.data_ptr(), tags.data_ptr() + self.n * self.tag_bytes
+            for own in (self.tags, self.ok):
+                if e0 < own.data_ptr() + _nbytes(own) and own.data_ptr() < e1:
+                    raise ValueError("tags overlaps the batch's own tags / verdicts, which this run overwrites: "
+                                     "pass a copy (tags.clone())")
+        self._launch(True, ivs, tags, stream)
+        return self.outs, (self.ok.view(torch.bool) if self.n else self._empty((0,), torch.bool))
+
+    def ghash(self, stream=None) -> torch.Tensor:
+        """The hash half by itself (``otc_ghash_batch``): a device uint8
+        [n, 16] tensor, row m the GHASH under the key's H of record m's
+        ``pad16(AAD) || pad16(input) || lengths``."""
+        if self.n == 0:
+            return self._empty((0, 16), torch.uint8)
+        st = stream or torch.cuda.current_stream(self.device)
+        s = torch.empty((self.n, 16), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _lib().otc_ghash_batch(self._plan.data_ptr() + self._o_desc, self.n, self._tab.data_ptr(),
+                                        s.data_ptr(), self.lanes, ctypes.c_void_p(st.cuda_stream))
+        _native.check(rc, "otc_ghash_batch")
+        return s
+
+
+def gcm_batch_spans() -> list[int]:
+    """The batched GHASH kernel's own boundaries in hashed blocks (AAD, data
+    and length block together), smallest first (otc.h otc_gcm_batch_spans)."""
+    buf = (ctypes.c_uint64 * 16)()
+    n = _lib().otc_gcm_batch_spans(buf, 16)
+    return [int(v) for v in buf[:n]]
+
+
+def ghash_batch(xs, key: bytes, aads=None, lanes=None) -> torch.Tensor:
+    """GHASH of every record of a batch under ``key``'s hash subkey, length
+    block included: device uint8 [n, 16] (the hash kernel of ``GcmBatch``
+    alone)."""
+    xs = list(xs)
+    return GcmBatch(xs, key, outs=xs, aads=aads, lanes=lanes).ghash()
+
+
+def gcm_encrypt_batch(xs, key: bytes, ivs: torch.Tensor, aads=None, outs=None):
+    """Plan and run a ``GcmBatch`` once: ``(outs, tags)``."""
+    return GcmBatch(xs, key, outs=outs, aads=aads).encrypt(ivs)
+
+
+def gcm_decrypt_batch(xs, key: bytes, ivs: torch.Tensor, tags: torch.Tensor, aads=None, outs=None):
+    """Plan and run a ``GcmBatch`` once: ``(outs, ok)``; the tag length is
+    ``tags.shape[1]``."""
+    tb = int(tags.shape[1]) if isinstance(tags, torch.Tensor) and tags.dim() == 2 else 16
+    return GcmBatch(xs, key, outs=outs, aads=aads, tag_bytes=tb).decrypt(ivs, tags)
+
+
 def _seg_call(fn_name: str, x: torch.Tensor, key: bytes, iv0: bytes, segment_bytes: int, out, inplace_ok: bool,
               impl="auto"):
     _check_dev(x, "x")
