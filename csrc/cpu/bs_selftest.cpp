@@ -9,10 +9,94 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <utility>
+
 #include "aes.h"
 #include "otc_bitslice.h"
 
 using namespace otc_bs;
+
+/* ---- depth-first output transpose (tests/test_bs_dfs_cpu.py) -------------- */
+
+/* steps 0..3: transpose32_nib8<step>; 8..15: transpose32_quad<step - 8>; 16..19: transpose32_group8<step - 16> */
+template <int... G, int... Q>
+static void dfs_step(W *m, int step, std::integer_sequence<int, G...>, std::integer_sequence<int, Q...>)
+{
+    ((step == G ? transpose32_nib8<G>(m) : (void)0), ...);
+    ((step == 8 + Q ? transpose32_quad<Q>(m) : (void)0), ...);
+    ((step == 16 + G ? transpose32_group8<G>(m) : (void)0), ...);
+}
+
+/* m[32] <- transpose32_bytes, then the given pieces in the given order
+ * (dfs_step codes).  A complete transpose is every group8 once, or every
+ * nib8 and quad once with nib8<G> before quad<2G> and quad<2G+1>.
+ * -1: a step out of range. */
+extern "C" int otc_bs_dfs_transpose(uint32_t *m, const int *steps, int nsteps)
+{
+    for (int i = 0; i < nsteps; ++i) {
+        const int s = steps[i];
+        if (!((s >= 0 && s < 4) || (s >= 8 && s < 16) || (s >= 16 && s < 20))) return -1;
+    }
+    transpose32_bytes(m);
+    for (int i = 0; i < nsteps; ++i)
+        dfs_step(m, steps[i], std::make_integer_sequence<int, 4>{}, std::make_integer_sequence<int, 8>{});
+    return 0;
+}
+
+/* Host model of the CTR output phase of one lane: planes[128] in (the state
+ * after the last round, before the last AddRoundKey), rk[4] the last round
+ * key, pt[32 * 4] the plaintext words of the 32 slots; out[32 * 4] = slot k's
+ * ks ^ rk ^ pt.  dfs = 0: four transpose32, then the slots in order (the old
+ * phase); 1: ctr_out_dfs as the kernel instantiates it (ls LDS slots, first
+ * = ls + the early register slots, cap), with a register file that a slot's
+ * plaintext enters only at its issue().  order[32] (optional) receives the
+ * event log of the register slots: order[j] = the number of slots emitted
+ * when slot j was issued (-1 for slots below `first`).
+ * Returns 0, or: -1 unsupported (ls, first, cap), 1 a slot emitted before its
+ * plaintext was issued, 2 a slot issued or emitted twice / never. */
+extern "C" int otc_bs_ctr_out_model(const uint32_t *planes, const uint32_t *rk, const uint32_t *pt, uint32_t *out,
+                                    int dfs, int ls, int first, int cap, int *order)
+{
+    W s[128];
+    for (int p = 0; p < 128; ++p) s[p] = planes[p];
+    int issued[32], emitted[32], nemit = 0, err = 0;
+    uint32_t reg[32][4];
+    for (int k = 0; k < 32; ++k) {
+        issued[k] = k < first; /* staged in LDS / loaded before the phase */
+        emitted[k] = 0;
+        for (int w = 0; w < 4; ++w) reg[k][w] = issued[k] ? pt[4 * k + w] : 0xDEADBEEFu;
+        if (order) order[k] = -1;
+    }
+    auto emit = [&](int k) {
+        if (!issued[k]) err = err ? err : 1;
+        if (emitted[k]++) err = err ? err : 2;
+        for (int w = 0; w < 4; ++w) out[4 * k + w] = x3(reg[k][w], s[32 * w + k], rk[w]);
+        ++nemit;
+    };
+    auto issue = [&](int j) {
+        if (j < first || issued[j]++) err = err ? err : 2;
+        for (int w = 0; w < 4; ++w) reg[j][w] = pt[4 * j + w];
+        if (order) order[j] = nemit;
+    };
+    if (!dfs) {
+        for (int w = 0; w < 4; ++w) transpose32(s + 32 * w);
+        for (int j = first; j < 32; ++j) issue(j);
+        for (int k = 0; k < 32; ++k) emit(k);
+    } else if (ls == 8 && first == 10 && cap == 36) {
+        ctr_out_dfs<8, 10, 36>(s, emit, issue); /* the kernel's default */
+    } else if (ls == 8 && first == 10 && cap == 34) {
+        ctr_out_dfs<8, 10, 34>(s, emit, issue); /* a shorter look-ahead */
+    } else if (ls == 12 && first == 14 && cap == 36) {
+        ctr_out_dfs<12, 14, 36>(s, emit, issue);
+    } else if (ls == 0 && first == 4 && cap == 40) {
+        ctr_out_dfs<0, 4, 40>(s, emit, issue);
+    } else {
+        return -1;
+    }
+    for (int k = 0; k < 32; ++k)
+        if (!issued[k] || emitted[k] != 1) err = err ? err : 2;
+    return err;
+}
 
 extern "C" int otc_bitslice_selftest(int verbose)
 {
@@ -61,11 +145,22 @@ extern "C" int otc_bitslice_selftest(int verbose)
             z ^= z << 13; z ^= z >> 7; z ^= z << 17;
             a[i] = b[i] = (W)(z >> 11);
         }
+        W c[32];
+        for (int i = 0; i < 32; ++i) c[i] = a[i];
         transpose32(a);
         transpose32_ref(b);
         for (int i = 0; i < 32; ++i)
             if (a[i] != b[i]) {
                 if (verbose) printf("  transpose32 mismatch (trial %d, word %d)\n", t, i);
+                ++fails;
+                break;
+            }
+        /* depth-first pieces: byte stages, then the groups last to first */
+        const int rev[4] = {19, 18, 17, 16};
+        otc_bs_dfs_transpose(c, rev, 4);
+        for (int i = 0; i < 32; ++i)
+            if (c[i] != b[i]) {
+                if (verbose) printf("  depth-first transpose mismatch (trial %d, word %d)\n", t, i);
                 ++fails;
                 break;
             }

@@ -32,8 +32,15 @@
  *     (tools/mixcol_search.py; the textbook forms take 76-80);
  *   - CTR: the plaintext of the first 8 slots goes straight to LDS by the
  *     DMA path (no VGPRs) once rounds 1-2 have consumed the counter-cache
- *     table loads, and lands while the other rounds run; the other slots are
- *     loaded 8 slots ahead of their use in groups of 4;
+ *     table loads, and lands while the other rounds run; slots 8-9 are loaded
+ *     into registers at the end of the rounds;
+ *   - CTR: a depth-first output phase (OTC_BS_OUT_DFS): the byte stages of
+ *     the four output transposes first, then per quad of slots the bit stages
+ *     in all four word columns, the quad's XOR + stores, and the plaintext
+ *     loads of later slots into the registers its keystream freed -- the same
+ *     instructions as four whole transposes, ordered so that >= 220 VALU
+ *     instructions lie between every load and the wait that needs it (35-56
+ *     with all transposes first; tools/isa_load_distance.py);
  *   - a bulk launch compiled for full tasks only, whose load / store
  *     phases are straight-line code with exact vmcnt waits, plus a
  *     one-workgroup launch for a partial first / last task (BS_FULL_ONLY /
@@ -363,10 +370,14 @@ __device__ __forceinline__ void rounds_table(W *s, ktab_ptr tp)
 /* Default task.  LS: CTR plaintext slots prefetched into LDS (layout
  * [wave][slot][lane] x 16 B, exactly the lane-linear image the DMA writes;
  * each lane reads its own 16 B back with a conflict-free ds_read_b128).
- * PRE: register slots issued before the output transposes, whose ~1k VALU
- * ops cover their latency.  D: the other register slots are loaded D slots
- * ahead of use, in groups of 4, as the keystream of consumed slots frees
- * registers (loading all of them up front spills at 3 waves). */
+ * PRE: register slots issued before the output transposes, whose VALU ops
+ * cover their latency (all ~1k of them in the old phase; the 256 of the byte
+ * stages and the first quad's 128 in the depth-first one).  D (the old
+ * phase: every mode but CTR, and OTC_BS_OUT_DFS=0): the other register slots
+ * are loaded D slots ahead of use, in groups of 4, as the keystream of
+ * consumed slots frees registers (loading all of them up front spills at 3
+ * waves).  The depth-first CTR phase has its own look-ahead, OTC_BS_DFS_CAP
+ * below. */
 /* register plaintext slots issued before the output transposes (2: with the
  * 81-LUT S-box (27 live planes at its peak) 4 early slots spilled in the
  * output phase; with the 79-LUT one (24) they no longer spill but measured
@@ -380,6 +391,30 @@ __device__ __forceinline__ void rounds_table(W *s, ktab_ptr tp)
 #ifndef OTC_BS_PRE
 #define OTC_BS_PRE 2
 #endif
+/* CTR output phase (the t3 launches, bulk and edge).  OTC_BS_OUT_DFS 1:
+ * depth-first -- the byte stages of the four output transposes, then per
+ * quad of slots the bit stages, the XOR + stores and the next loads
+ * (otc_bitslice.h ctr_out_dfs), so ~100 transposition instructions lie
+ * between a quad's loads and the next quad's, and no register load is issued
+ * between the PRE early ones and the first staged-LDS read (whose
+ * conservative vmcnt(0) then covers only loads issued a whole byte stage
+ * earlier).  D does not apply: the look-ahead is what OTC_BS_DFS_CAP slots
+ * of 4 live registers (keystream + plaintext) allow, 36 = the peak of the
+ * old phase and the most that fits: 38, 40 and PRE 4 all spill (20-36 B of
+ * scratch, 168 VGPRs).  0: all four transposes, then the slots in order with
+ * loads D slots ahead (the A/B arm, and what every other mode and the claim
+ * kernels run).  A/B, 64 GiB in place, 3 interleaved reps
+ * (profiles/r7/dfs_ab/): AES-128 CTR 1735-1745 vs 1712-1718 GB/s, at 4 GiB
+ * 1700-1705 vs 1681-1687, AES-256 1313-1315 vs 1306-1312, at 0.782-0.784 vs
+ * 0.789-0.792 J/GB; same 12,802 VALU per task. */
+#ifndef OTC_BS_OUT_DFS
+#define OTC_BS_OUT_DFS 1
+#endif
+#ifndef OTC_BS_DFS_CAP
+#define OTC_BS_DFS_CAP 36
+#endif
+constexpr bool BS_OUT_DFS = OTC_BS_OUT_DFS != 0;
+constexpr int BS_DFS_CAP = OTC_BS_DFS_CAP;
 template <int NR, int MODE, int LS, bool CACHE, bool FO, int MIX = 2, int PRE = OTC_BS_PRE, int D = 8>
 __device__ __forceinline__ void aes_bs_task(const BsParams &P, const otc_aes_key &K, uint4 *stage,
                                             int64_t claimed = -1)
@@ -491,9 +526,9 @@ __device__ __forceinline__ void aes_bs_task(const BsParams &P, const otc_aes_key
         const int64_t si = tstart + (int64_t)lane + 64 * k;
         return full || (si >= 0 && (uint64_t)si < P.nblocks);
     };
-    /* register-loaded plaintext (slots LS..31); none is issued behind a
-     * store -- vmcnt is in order on gfx9, so such a load would also wait for
-     * the stores */
+    /* register-loaded plaintext (slots LS..31).  vmcnt is in order on gfx9:
+     * a load issued behind stores also waits for them, so the loads go out
+     * in groups right after a quad's stores, well ahead of their use */
     /* the block XORed into the output: CTR the plaintext, CBC decrypt the
      * previous ciphertext block (the IV for block 0 of a whole-stream call),
      * CFB decrypt the ciphertext block itself */
@@ -524,12 +559,6 @@ __device__ __forceinline__ void aes_bs_task(const BsParams &P, const otc_aes_key
 #pragma unroll
     for (int j = 0; j < LS + PRE_; ++j) issue(j);
     sched_fence();
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        transpose32(s + 32 * w);
-        pin_n(s + 32 * w, 32);
-        sched_fence();
-    }
     /* last round key; decryption adds the 0x05 the post-map L leaves */
     constexpr uint32_t KD = DEC ? 0x05050505u : 0u;
     const uint32_t k0 = K.rk[4 * NR + 0] ^ KD, k1 = K.rk[4 * NR + 1] ^ KD, k2 = K.rk[4 * NR + 2] ^ KD,
@@ -542,18 +571,35 @@ __device__ __forceinline__ void aes_bs_task(const BsParams &P, const otc_aes_key
         o.w = x3(x.w, s[96 + k], k3);
         return o;
     };
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        if ((k & 3) == 0) {
-            sched_fence();
-#pragma unroll
-            for (int j = LS + PRE_; j < 32; ++j)
-                if ((j - D_ < 0 ? 0 : ((j - D_) & ~3)) == k) issue(j);
-        }
+    /* XOR and store slot k (transposed: s[32w + k] = word w of its block) */
+    auto emit = [&](int k) {
         if (slot_ok(k)) {
             const uint4 o = XIN ? ks_xor(k, k < LS ? stage[(wave * LS + k) * 64 + (lo >> 4)] : pt[k])
                                 : make_uint4(s[k] ^ k0, s[32 + k] ^ k1, s[64 + k] ^ k2, s[96 + k] ^ k3);
             st_stream(ob + lo + 1024u * k, o);
+        }
+    };
+    if constexpr (BS_OUT_DFS && MODE == BS_CTR && LS + PRE_ >= 4) {
+        /* depth-first: byte stages, then per quad of slots the bit stages in
+         * all four columns, the quad's XOR + stores, and the loads that fit
+         * in the registers it freed (otc_bitslice.h ctr_out_dfs) */
+        ctr_out_dfs<LS, LS + PRE_, BS_DFS_CAP>(s, emit, issue);
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            transpose32(s + 32 * w);
+            pin_n(s + 32 * w, 32);
+            sched_fence();
+        }
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            if ((k & 3) == 0) {
+                sched_fence();
+#pragma unroll
+                for (int j = LS + PRE_; j < 32; ++j)
+                    if ((j - D_ < 0 ? 0 : ((j - D_) & ~3)) == k) issue(j);
+            }
+            emit(k);
         }
     }
 }

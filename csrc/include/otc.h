@@ -578,6 +578,11 @@ int otc_multi_ctr_resident(int ngpus, void *const *dev_bufs, size_t shard_bytes,
 
 /* Library self description / tests */
 int otc_bitslice_selftest(int verbose);
+/* host runs of the depth-first output transpose and of the bitsliced CTR
+ * output phase built on it (csrc/cpu/bs_selftest.cpp) */
+int otc_bs_dfs_transpose(uint32_t *m, const int *steps, int nsteps);
+int otc_bs_ctr_out_model(const uint32_t *planes, const uint32_t *rk, const uint32_t *pt, uint32_t *out, int dfs,
+                         int ls, int first, int cap, int *order);
 const char *otc_build_info(void);
 /* JSON object naming the HIP runtime / driver and RCCL versions this process
  * runs on and the mapped libamdhip64 / librccl paths (/proc/self/maps): in a

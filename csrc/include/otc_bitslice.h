@@ -871,6 +871,143 @@ OTC_HD void transpose32(W *m)
     transpose_bits<1>(m, 0x55555555u);
 }
 
+/* ---- depth-first transpose ------------------------------------------------
+ * The stages of transpose32 commute: after the two byte stages, registers
+ * 8g..8g+7 are an independent 8x8-block problem whose result is output words
+ * 8g..8g+7, and after its 4-bit stage registers 4q..4q+3 yield words
+ * 4q..4q+3.  A caller can therefore finish, use and release a few output
+ * words at a time (the CTR output phase, ctr_out_dfs below) instead of all 32
+ * at once.  Same instructions as transpose32, in another order; every index
+ * is a compile-time constant (template parameters, unrolled loops). */
+
+/* the 16- and 8-bit stages of transpose32 and nothing else */
+OTC_HD void transpose32_bytes(W *m)
+{
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const W a = m[k], b = m[k | 16];
+        m[k] = perm_b(b, a, 0x05040100u);
+        m[k | 16] = perm_b(b, a, 0x07060302u);
+    }
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+        if (k & 8) continue;
+        const W a = m[k], b = m[k | 8];
+        m[k] = perm_b(b, a, 0x06020400u);
+        m[k | 8] = perm_b(b, a, 0x07030501u);
+    }
+}
+
+/* transpose_bits<J> restricted to registers LO..LO+N-1 (N a multiple of 2J,
+ * LO of N) */
+template <int J, int LO, int N>
+OTC_HD void transpose_bits_in(W *m, W mk)
+{
+    static_assert(N % (2 * J) == 0 && LO % N == 0 && LO + N <= 32, "whole swap pairs only");
+#pragma unroll
+    for (int k = LO; k < LO + N; ++k) {
+        if (k & J) continue;
+        const W a = m[k], b = m[k | J];
+        m[k] = bsel(mk << J, b << J, a);
+        m[k | J] = bsel(mk, a >> J, b);
+    }
+}
+
+/* after transpose32_bytes: the 4-bit stage of registers 8G..8G+7 (G < 4) */
+template <int G>
+OTC_HD void transpose32_nib8(W *m)
+{
+    transpose_bits_in<4, 8 * G, 8>(m, 0x0F0F0F0Fu);
+}
+
+/* after transpose32_nib8<Q / 2>: the 2- and 1-bit stages of registers
+ * 4Q..4Q+3, which then hold output words 4Q..4Q+3 of transpose32 */
+template <int Q>
+OTC_HD void transpose32_quad(W *m)
+{
+    transpose_bits_in<2, 4 * Q, 4>(m, 0x33333333u);
+    transpose_bits_in<1, 4 * Q, 4>(m, 0x55555555u);
+}
+
+/* after transpose32_bytes: finish output words 8G..8G+7; the four groups may
+ * be finished in any order */
+template <int G>
+OTC_HD void transpose32_group8(W *m)
+{
+    transpose32_nib8<G>(m);
+    transpose32_quad<2 * G>(m);
+    transpose32_quad<2 * G + 1>(m);
+}
+
+/* pin 4 x 4 values with one asm (pin8: every asm boundary can cost an s_nop) */
+OTC_HD void pin4x4(W *a, W *b, W *c, W *d)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile(""
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]),
+                   "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]));
+#else
+    (void)a, (void)b, (void)c, (void)d;
+#endif
+}
+
+/* Depth-first CTR output phase of one task: s[128] = the keystream planes
+ * after the last round.  Slots (output words) are finished four at a time in
+ * all four word columns; emit(k) XORs and stores slot k; issue(j) starts the
+ * plaintext load of slot j.  Slots below FIRST need no issue() here (staged
+ * in LDS, or loaded before the call); FIRST >= 4, so quad 0 needs none.
+ *
+ * Look-ahead: a slot's keystream (4 registers) is dead once it is emitted, so
+ * after quad Q the loads run as far ahead as CAP allows: the live keystream
+ * slots, 32 - 4(Q+1), plus the plaintext slots in registers, from
+ * max(4(Q+1), LS) up to the limit, stay <= CAP slots of 4 registers.  LS =
+ * slots that never occupy registers.  With LS 8, FIRST 10, CAP 36 (144
+ * registers, the old phase's peak): 10-15 after quad 0, 16-19 after quad 1,
+ * 20-27 after quad 2, 28-31 after quad 3 -- every load has at least two
+ * quads' transposition (~200 VALU instructions) before its first use, and no
+ * load is issued before the first emit. */
+constexpr int ctr_out_dfs_limit(int q, int ls, int first, int cap)
+{
+    const int done = 4 * (q + 1);
+    const int lim = cap - 32 + done + (done > ls ? done : ls);
+    return q < 0 || lim < first ? first : lim > 32 ? 32 : lim;
+}
+
+template <int Q, int LS, int FIRST, int CAP, class Emit, class Issue>
+OTC_HD void ctr_out_dfs_quad(W *s, Emit &emit, Issue &issue)
+{
+    constexpr int LIM = ctr_out_dfs_limit(Q, LS, FIRST, CAP);
+    /* every slot is in registers (or LDS) before the quad that emits it */
+    static_assert(Q == 7 || LIM >= 4 * (Q + 2), "look-ahead too short: raise CAP");
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (Q % 2 == 0) transpose32_nib8<Q / 2>(s + 32 * w);
+        transpose32_quad<Q>(s + 32 * w);
+    }
+    pin4x4(s + 4 * Q, s + 32 + 4 * Q, s + 64 + 4 * Q, s + 96 + 4 * Q);
+    sched_fence();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) emit(4 * Q + i);
+    sched_fence();
+#pragma unroll
+    for (int j = ctr_out_dfs_limit(Q - 1, LS, FIRST, CAP); j < LIM; ++j) issue(j);
+    sched_fence();
+    if constexpr (Q < 7) ctr_out_dfs_quad<Q + 1, LS, FIRST, CAP>(s, emit, issue);
+}
+
+template <int LS, int FIRST, int CAP, class Emit, class Issue>
+OTC_HD void ctr_out_dfs(W *s, Emit emit, Issue issue)
+{
+    static_assert(FIRST >= 4 && FIRST >= LS && FIRST <= 32, "quad 0's slots are ready before the phase");
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        transpose32_bytes(s + 32 * w);
+        pin_n(s + 32 * w, 32);
+        sched_fence();
+    }
+    ctr_out_dfs_quad<0, LS, FIRST, CAP>(s, emit, issue);
+}
+
 /* Reference transpose (host tests). */
 inline void transpose32_ref(W *m)
 {

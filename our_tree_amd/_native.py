@@ -184,6 +184,9 @@ def _declare_cpu(lib):
         "AES_CTR_encrypt": (None, [c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_ulong, c_u8p, c_int]),
         "AES_CTR_encrypt_at": (None, [c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_ulong, c_u8p, c_int, ctypes.c_ulonglong]),
         "otc_bitslice_selftest": (c_int, [c_int]),
+        "otc_bs_dfs_transpose": (c_int, [P(ctypes.c_uint32), P(c_int), c_int]),
+        "otc_bs_ctr_out_model": (c_int, [P(ctypes.c_uint32), P(ctypes.c_uint32), P(ctypes.c_uint32),
+                                         P(ctypes.c_uint32), c_int, c_int, c_int, c_int, P(c_int)]),
         "otc_rccl_nrounds": (c_u64, [c_u64, c_int, c_u64]),
         "otc_rccl_plan_piece": (c_int, [c_u64, c_int, c_u64, c_u64, c_int, P(RcclPiece)]),
         "otc_rccl_halo_start": (c_u64, [c_u64, c_u64, c_u64]),
