@@ -35,9 +35,9 @@ endif
 LIBDIR := our_tree_amd/lib
 OBJ    := build/obj
 
-CPU_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/rc4.c csrc/cpu/aesni.c csrc/cpu/numa.c csrc/cpu/rccl_plan.c
+CPU_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/rc4.c csrc/cpu/aesni.c csrc/cpu/numa.c csrc/cpu/rccl_plan.c csrc/cpu/chacha.c
 CPU_OBJ := $(patsubst csrc/cpu/%.c,$(OBJ)/cpu/%.o,$(CPU_SRC)) $(OBJ)/cpu/bs_selftest.o
-HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_bs.hip csrc/hip/stream_ops.hip
+HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/stream_ops.hip
 HIP_OBJ := $(patsubst csrc/hip/%.hip,$(OBJ)/hip/%.o,$(HIP_SRC)) $(OBJ)/hip/engine.o $(OBJ)/hip/split.o $(OBJ)/hip/pipeline.o
 
 BINS := bin/test bin/aes_test bin/aes_ecb_e bin/aes_ecb_d bin/otbench bin/bc_test
@@ -162,11 +162,11 @@ clean:
 	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
 
 # Host sanitizers over the threaded CPU paths (also tests/test_sanitizers_cpu.py)
-SAN_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cli/san_driver.c
+SAN_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/chacha.c csrc/cli/san_driver.c
 san-check:
 	@mkdir -p build/san
-	$(CC) -O1 -g -std=gnu99 -Icsrc/include -fsanitize=thread $(SAN_SRC) -o build/san/tsan -lpthread
-	$(CC) -O1 -g -std=gnu99 -Icsrc/include -fsanitize=address,undefined -fno-sanitize-recover=undefined $(SAN_SRC) -o build/san/asan -lpthread
+	$(CC) -O1 -g -std=gnu99 -Icsrc/include -DOTC_SAN_CHACHA -fsanitize=thread $(SAN_SRC) -o build/san/tsan -lpthread
+	$(CC) -O1 -g -std=gnu99 -Icsrc/include -DOTC_SAN_CHACHA -fsanitize=address,undefined -fno-sanitize-recover=undefined $(SAN_SRC) -o build/san/asan -lpthread
 	TSAN_OPTIONS=halt_on_error=1 ./build/san/tsan
 	./build/san/asan
 .PHONY: san-check

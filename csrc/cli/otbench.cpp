@@ -5,6 +5,7 @@
  *
  *   otbench --mode ctr|ecb|ecb-dec|cbc-dec|cbc-enc-seg|cfb-enc-seg|cfb-dec-seg|cbc-dec-seg|cfb-dec|ctr-stream|xor|rc4
  *                  |ecb-split|ecbdec-split|cbcdec-split|cfbdec-split|ctr-split|xts-enc|xts-dec|gcm-enc|gcm-dec
+ *                  |chacha20|poly1305|chachapoly-enc|chachapoly-dec
  *           [--bits 128] [--bytes 1G] [--iters 20] [--warmup 3]
  *           [--impl auto|ttable|bitslice|split] [--inplace] [--verify] [--clock]
  *           [--mark]                        "OTB_MARK start|end" on stderr around the timed loop
@@ -22,6 +23,12 @@
  *                                           the IV (>= 1; 12 is GCM's fast path).  --bytes may be any byte
  *                                           count; --verify also recomputes the tag on the host, and the JSON
  *                                           line carries "tag" and "tag_ok"
+ *           chacha20 / poly1305 / chachapoly-enc / chachapoly-dec (RFC 8439): the key is 32 bytes whatever
+ *                                           --bits says, the nonce 12 bytes, the data starts at block counter
+ *                                           1; --bytes may be any byte count; --aad as for gcm-*.  poly1305
+ *                                           hashes the input and writes only the tag; its --verify recomputes
+ *                                           the tag over the whole input on the host, and --corrupt-at flips
+ *                                           tag byte OFF % 16
  *           [--share 0.2]                   *-split: the bitsliced kernel's share of the
  *                                           blocks, run CONCURRENTLY with the T-table kernel
  *                                           on the rest (two streams, co-resident per CU) --
@@ -53,6 +60,7 @@
 extern "C" {
 #include "aes.h"
 #include "arc4.h"
+#include "chacha.h"
 #include "otc.h"
 }
 
@@ -91,6 +99,7 @@ struct OpArg {
     otc_aes_key *k;
     otc_xts_key *xk; /* xts-enc / xts-dec */
     otc_gcm_key *gk; /* gcm-enc / gcm-dec: key, IV, AAD and 16 device bytes for the computed tag */
+    const uint8_t *ckey; /* the chacha modes' 32-byte key */
     std::vector<uint8_t> giv, gaad;
     void *tag_dev;
     uint8_t iv[16];
@@ -101,6 +110,11 @@ struct OpArg {
 
 static bool is_xts(const std::string &m) { return m == "xts-enc" || m == "xts-dec"; }
 static bool is_gcm(const std::string &m) { return m == "gcm-enc" || m == "gcm-dec"; }
+static bool is_chachapoly(const std::string &m) { return m == "chachapoly-enc" || m == "chachapoly-dec"; }
+/* the modes of csrc/hip/chacha.hip: a 32-byte key, a 12-byte nonce (the first 12 bytes of iv), data from counter 1 */
+static bool is_chacha(const std::string &m) { return m == "chacha20" || m == "poly1305" || is_chachapoly(m); }
+/* the modes that leave a 16-byte tag in tag_dev */
+static bool has_tag(const std::string &m) { return is_gcm(m) || m == "poly1305" || is_chachapoly(m); }
 
 static bool is_split(const std::string &m)
 {
@@ -171,6 +185,12 @@ static int run_op(void *p)
     if (is_gcm(c.mode))
         return otc_aes_gcm(a->in, a->out, c.bytes, a->gk, c.mode == "gcm-dec" ? OTC_DIR_DECRYPT : OTC_DIR_ENCRYPT,
                            a->giv.data(), a->giv.size(), a->gaad.data(), a->gaad.size(), a->tag_dev, c.impl, nullptr);
+    if (c.mode == "chacha20") return otc_chacha20(a->in, a->out, c.bytes, a->ckey, a->iv, 1, nullptr);
+    if (c.mode == "poly1305") return otc_poly1305(a->in, c.bytes, a->ckey, a->tag_dev, nullptr);
+    if (is_chachapoly(c.mode))
+        return otc_chacha20_poly1305(a->in, a->out, c.bytes, a->ckey,
+                                     c.mode == "chachapoly-dec" ? OTC_DIR_DECRYPT : OTC_DIR_ENCRYPT, a->iv,
+                                     a->gaad.data(), a->gaad.size(), a->tag_dev, nullptr);
     if (c.mode == "xor") return otc_xor(a->in, a->out, a->out, c.bytes, nullptr);
     if (c.mode == "rc4") return otc_rc4_multi(a->keys, (int)c.keylen, c.streams, c.len, c.drop, a->in, a->out, nullptr);
     return OTC_ERR_ARG;
@@ -213,10 +233,11 @@ static std::vector<std::pair<size_t, size_t>> sample_ranges(const Cfg &c)
         if (c.bytes > (4ull << 30) + k * c.seg) r.push_back({((4ull << 30) / c.seg) * c.seg - c.seg, 2 * c.seg});
     } else {
         const size_t S = std::min<size_t>(c.bytes, 64 << 10);
-        /* samples start on a block boundary of the mode: 16m, or 1 + 16m for
-         * ctr-stream (its body starts after a 1-byte head) */
-        const size_t b = c.mode == "ctr-stream" ? 1 : 0;
-        auto down = [&](size_t o) { return o < b ? 0 : ((o - b) / 16) * 16 + b; };
+        /* samples start on a block boundary of the mode: 16m (64m for the
+         * chacha modes), or 1 + 16m for ctr-stream (its body starts after a
+         * 1-byte head) */
+        const size_t b = c.mode == "ctr-stream" ? 1 : 0, blk = is_chacha(c.mode) ? 64 : 16;
+        auto down = [&](size_t o) { return o < b ? 0 : ((o - b) / blk) * blk + b; };
         r.push_back({0, S});
         const size_t m = down((c.bytes - S) / 2);
         r.push_back({m, std::min(S, c.bytes - m)});
@@ -285,6 +306,9 @@ static bool oracle(const Cfg &c, const uint8_t key[64], const uint8_t iv0[16], c
         lo += 1u + (uint32_t)(s.off / 16);
         for (int i = 0; i < 4; ++i) ctr[12 + i] = (uint8_t)(lo >> (24 - 8 * i));
         aes_crypt_ctr32(&g, s.len, ctr, in, ref.data());
+    } else if (m == "chacha20" || is_chachapoly(m)) {
+        /* both directions XOR the keystream from block counter 1; the block at byte s.off is 1 + s.off / 64 */
+        if (chacha20_crypt(key, iv0, (uint32_t)(1 + s.off / 64), in, ref.data(), s.len)) return false;
     } else if (m == "ctr-stream") {
         /* the run's context: nc_off 15 with a zero stream block, so data byte 0
          * passes through and byte p >= 1 uses keystream byte (p - 1) of the
@@ -446,6 +470,44 @@ static bool gcm_expected_tag(const Cfg &c, const OpArg &a, const uint8_t *key, c
     return true;
 }
 
+/* the Poly1305 tag of a poly1305 or chachapoly-* run over the n bytes in `buf`, copied to the host in pieces:
+ * poly1305 hashes them under the key itself, the AEAD under block 0's key as pad16(AAD) || pad16(C) || lengths */
+static bool poly_expected_tag(const Cfg &c, const OpArg &a, const uint8_t *key, const void *buf, CopyFn cp, uint8_t tag[16])
+{
+    const bool aead = is_chachapoly(c.mode);
+    poly1305_state st;
+    uint8_t b0[64];
+    if (aead) {
+        chacha20_block(key, a.iv, 0, b0);
+        poly1305_init(&st, b0);
+        poly1305_pad16(&st, a.gaad.data(), a.gaad.size());
+    } else {
+        poly1305_init(&st, key);
+    }
+    std::vector<uint8_t> h(std::min<size_t>(c.bytes, 64u << 20));
+    for (size_t off = 0; off < c.bytes; off += h.size()) {
+        const size_t step = std::min(h.size(), c.bytes - off);
+        if (cp(h.data(), (const uint8_t *)buf + off, step)) return false;
+        poly1305_blocks(&st, h.data(), step / 16); /* only the last piece has a short block */
+        if (step % 16) {
+            if (aead)
+                poly1305_pad16(&st, h.data() + step - step % 16, step % 16);
+            else
+                poly1305_last(&st, h.data() + step - step % 16, step % 16);
+        }
+    }
+    if (aead) {
+        uint8_t lb[16];
+        for (int i = 0; i < 8; ++i) {
+            lb[i] = (uint8_t)((uint64_t)a.gaad.size() >> (8 * i));
+            lb[8 + i] = (uint8_t)((uint64_t)c.bytes >> (8 * i));
+        }
+        poly1305_blocks(&st, lb, 1);
+    }
+    poly1305_finish(&st, tag);
+    return true;
+}
+
 static const char *verdict(bool asked, int v) { return !asked ? "null" : v == 1 ? "true" : "false"; }
 
 int main(int argc, char **argv)
@@ -494,7 +556,8 @@ int main(int argc, char **argv)
     static const char *modes[] = {"ctr", "ecb", "ecb-dec", "cbc-dec", "cbc-enc-seg", "cfb-enc-seg", "cfb-dec-seg",
                                   "cbc-dec-seg",
                                   "cfb-dec", "ctr-stream", "xor", "rc4", "ecb-split", "ecbdec-split", "cbcdec-split",
-                                  "cfbdec-split", "ctr-split", "xts-enc", "xts-dec", "gcm-enc", "gcm-dec"};
+                                  "cfbdec-split", "ctr-split", "xts-enc", "xts-dec", "gcm-enc", "gcm-dec",
+                                  "chacha20", "poly1305", "chachapoly-enc", "chachapoly-dec"};
     bool known = false;
     for (const char *m : modes) known |= c.mode == m;
     if (!known) {
@@ -502,8 +565,16 @@ int main(int argc, char **argv)
         return 2;
     }
     if (c.mode == "rc4") c.bytes = c.streams * c.len;
-    if (c.mode != "ctr" && c.mode != "ctr-stream" && c.mode != "xor" && c.mode != "rc4" && !is_gcm(c.mode))
+    if (c.mode != "ctr" && c.mode != "ctr-stream" && c.mode != "xor" && c.mode != "rc4" && !is_gcm(c.mode) && !is_chacha(c.mode))
         c.bytes &= ~(size_t)15;
+    if (is_chacha(c.mode) && (uint64_t)c.bytes > CHACHA20_POLY1305_MAX_BYTES) {
+        fprintf(stderr, "chacha: --bytes is at most (2^32 - 1) * 64\n");
+        return 2;
+    }
+    if (c.mode == "poly1305" && c.inplace) {
+        fprintf(stderr, "poly1305 writes only a tag: --inplace has no meaning\n");
+        return 2;
+    }
     if (is_gcm(c.mode) && (c.ivlen == 0 || c.bytes > AES_GCM_MAX_BYTES)) {
         fprintf(stderr, "gcm: --ivlen is at least 1, --bytes at most 2^36 - 32\n");
         return 2;
@@ -558,7 +629,8 @@ int main(int argc, char **argv)
     a.k = &k;
     a.xk = &xk;
     a.gk = &gk;
-    if (is_gcm(c.mode)) {
+    a.ckey = key;
+    if (is_gcm(c.mode) || is_chachapoly(c.mode)) {
         a.giv.resize(c.ivlen);
         a.gaad.resize(c.aad);
         for (size_t i = 0; i < c.ivlen; ++i) a.giv[i] = (uint8_t)(0xF0 + i);
@@ -631,14 +703,15 @@ int main(int argc, char **argv)
         }
     }
     a.in = otc_dev_malloc(c.bytes);
-    a.out = c.inplace ? a.in : otc_dev_malloc(c.bytes);
+    /* poly1305 has no output buffer: its result is the tag */
+    a.out = c.inplace || c.mode == "poly1305" ? a.in : otc_dev_malloc(c.bytes);
     if (!a.in || !a.out) {
         fprintf(stderr, "device alloc failed: %s\n", otc_last_error());
         return 1;
     }
     otc_fill_random(a.in, c.bytes, 42, nullptr);
-    if (!c.inplace) otc_fill_random(a.out, c.bytes, 43, nullptr);
-    if (is_gcm(c.mode) && !(a.tag_dev = otc_dev_malloc(16))) {
+    if (a.out != a.in) otc_fill_random(a.out, c.bytes, 43, nullptr);
+    if (has_tag(c.mode) && !(a.tag_dev = otc_dev_malloc(16))) {
         fprintf(stderr, "device alloc failed: %s\n", otc_last_error());
         return 1;
     }
@@ -664,7 +737,9 @@ int main(int argc, char **argv)
         std::vector<Sample> samples;
         /* the tag is over the ciphertext: the input of a decryption, hashed before the op overwrites it */
         if (c.mode == "gcm-dec" && !gcm_expected_tag(c, a, key, a.in, copy_d2h, want_tag)) return 1;
-        if (!snapshot(c, a, copy_d2h, samples)) {
+        if ((c.mode == "chachapoly-dec" || c.mode == "poly1305") && !poly_expected_tag(c, a, key, a.in, copy_d2h, want_tag))
+            return 1;
+        if (c.mode != "poly1305" && !snapshot(c, a, copy_d2h, samples)) {
             fprintf(stderr, "verify snapshot: %s\n", otc_last_error());
             return 1;
         }
@@ -672,10 +747,16 @@ int main(int argc, char **argv)
             fprintf(stderr, "op: %s\n", otc_last_error());
             return 1;
         }
-        if (c.corrupt_at >= 0 && corrupt(a.out, (size_t)c.corrupt_at, true)) return 1;
-        v = check_samples(c, a, copy_d2h, key, samples);
-        if (is_gcm(c.mode)) {
+        if (c.mode == "poly1305") { /* the tag is the whole result */
+            if (c.corrupt_at >= 0 && corrupt(a.tag_dev, (size_t)c.corrupt_at % 16, true)) return 1;
+            v = 1;
+        } else {
+            if (c.corrupt_at >= 0 && corrupt(a.out, (size_t)c.corrupt_at, true)) return 1;
+            v = check_samples(c, a, copy_d2h, key, samples);
+        }
+        if (has_tag(c.mode)) {
             if (c.mode == "gcm-enc" && !gcm_expected_tag(c, a, key, a.out, copy_d2h, want_tag)) return 1;
+            if (c.mode == "chachapoly-enc" && !poly_expected_tag(c, a, key, a.out, copy_d2h, want_tag)) return 1;
             if (otc_memcpy(tag, a.tag_dev, 16, OTC_D2H)) return 1;
             tag_ok = memcmp(tag, want_tag, 16) == 0;
             if (!tag_ok) {
@@ -759,7 +840,7 @@ int main(int argc, char **argv)
     strncat(clk, split_units, sizeof clk - strlen(clk) - 1);
     if (c.mode.size() > 6 && c.mode.compare(c.mode.size() - 6, 6, "-split") == 0)
         snprintf(clk + strlen(clk), sizeof clk - strlen(clk), "\"share\": %.3f, ", c.share);
-    if (is_gcm(c.mode)) { /* the tag of the last call (with --verify: of the verified one, read before the timed loop) */
+    if (has_tag(c.mode)) { /* the tag of the last call (with --verify: of the verified one, read before the timed loop) */
         if (!c.verify && (otc_device_sync() || otc_memcpy(tag, a.tag_dev, 16, OTC_D2H))) return 1;
         char hex[33];
         for (int i = 0; i < 16; ++i) snprintf(hex + 2 * i, 3, "%02x", tag[i]);
@@ -778,7 +859,7 @@ int main(int argc, char **argv)
            c.inplace ? "true" : "false", c.iters, ms, gbps, cpb, cus, clk_hz / 1e6, clk, runtime_json().c_str(),
            verdict(c.verify, v));
     otc_dev_free(a.in);
-    if (!c.inplace) otc_dev_free(a.out);
+    if (a.out != a.in) otc_dev_free(a.out);
     otc_dev_free(a.keys);
     otc_dev_free(a.tag_dev);
     otc_stream_destroy(a.sa);

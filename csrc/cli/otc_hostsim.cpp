@@ -25,6 +25,7 @@
 extern "C" {
 #include "aes.h"
 #include "arc4.h"
+#include "chacha.h"
 #include "otc.h"
 }
 
@@ -263,6 +264,34 @@ int otc_aes_gcm(const void *in, void *out, size_t n, const otc_gcm_key *k, int d
                          (const uint8_t *)in, (uint8_t *)out, (uint8_t *)tag_dev)
                ? fail(OTC_ERR_ARG, "gcm lengths")
                : OTC_OK;
+}
+
+int otc_chacha20(const void *in, void *out, size_t n, const uint8_t key[32], const uint8_t nonce[12], uint32_t counter,
+                 void *)
+{
+    return chacha20_crypt(key, nonce, counter, (const uint8_t *)in, (uint8_t *)out, n)
+               ? fail(OTC_ERR_ARG, "chacha20: the 32-bit block counter would pass 2^32 - 1")
+               : OTC_OK;
+}
+
+int otc_poly1305(const void *data, size_t n, const uint8_t key[32], void *tag_dev, void *)
+{
+    poly1305_mac(key, (const uint8_t *)data, n, (uint8_t *)tag_dev);
+    return OTC_OK;
+}
+
+int otc_chacha20_poly1305(const void *in, void *out, size_t n, const uint8_t key[32], int dir, const uint8_t nonce[12],
+                          const uint8_t *aad, size_t aad_len, void *tag_dev, void *)
+{
+    /* the computed tag in both directions: over out of an encryption, over in of a decryption */
+    int r;
+    if (dir == OTC_DIR_ENCRYPT) {
+        r = chacha20_poly1305_encrypt(key, nonce, aad, aad_len, (const uint8_t *)in, (uint8_t *)out, n, (uint8_t *)tag_dev);
+    } else {
+        r = chacha20_poly1305_tag(key, nonce, aad, aad_len, (const uint8_t *)in, n, (uint8_t *)tag_dev);
+        if (!r) r = chacha20_crypt(key, nonce, 1, (const uint8_t *)in, (uint8_t *)out, n);
+    }
+    return r ? fail(OTC_ERR_ARG, "chacha20_poly1305 lengths") : OTC_OK;
 }
 
 int otc_xor(const void *a, const void *b, void *out, size_t n, void *)

@@ -1,0 +1,583 @@
+/*
+ * chacha.hip -- ChaCha20 and Poly1305 (RFC 8439) on gfx950.
+ *
+ * ChaCha20.  One lane computes whole 64-byte blocks with the 16 state words
+ * in VGPRs.  Constants, key and nonce are kernel arguments by value (SGPRs);
+ * only the counter word differs per lane.  No tables, no LDS, no
+ * secret-dependent addresses or branches.
+ *
+ *   pass    64 blocks (4 KiB), one per lane.
+ *   wave    CC_RUN consecutive passes; a workgroup is CC_WAVES waves, the
+ *           grid one workgroup per CC_WAVES * CC_RUN passes (no stride loop).
+ *   bulk    whole passes of 16-byte aligned buffers: 16-byte non-temporal
+ *           loads and stores, the plaintext of a pass loaded before its
+ *           keystream is computed (so in place is safe: a lane stores only
+ *           over addresses it loaded).
+ *   edge    everything past the last whole pass, and the whole call when a
+ *           buffer is not 16-byte aligned: one block per lane, byte loads and
+ *           stores, every byte guarded by the length.
+ *
+ * Store layout of the bulk kernel: transposed.  Lane 4g + q computes block
+ * 16q + g of the pass and the four lanes of a quad exchange quarters (two DPP
+ * quad_perm butterflies, a 4x4 transpose of 16-byte pieces), after which load
+ * and store j of lane l cover bytes (64 j + l) * 16 ..: every load and store
+ * instruction of a wave covers 1 KiB contiguously.  The direct layout -- lane l
+ * owns block l, so the lanes of one 16-byte access are 64 bytes apart -- needs
+ * no exchange and measured 2.4-3.1 times SLOWER (633-691 against 1639-1967
+ * GB/s, docs/PERF.md "ChaCha20-Poly1305") and was removed.
+ *
+ * Poly1305.  tag = ((sum_{i=1..n} c_i r^(n-i+1)) mod p + s) mod 2^128 with
+ * p = 2^130 - 5 -- polynomial evaluation, the shape of GHASH (aes_gcm.hip),
+ * and the same tree:
+ *
+ *   pass        64 consecutive blocks, one per lane: a coalesced 1 KiB load.
+ *   batch       PL_BATCH = 4 passes: A = A C^4 + X0 C^3 + X1 C^2 + X2 C + X3
+ *               with C = r^64, the products accumulated in 64 bits and
+ *               carried once per batch.
+ *   wave span   m = PL_SPAN = 64 * PL_RUN = 2048 blocks (32 KiB).  Lane j
+ *               runs Horner under r^64 over blocks j, j + 64, ...
+ *   fold        lane j multiplies its accumulator by r^(63-j); the wave sums
+ *               the 64 products limb by limb: P = sum c_i r^(m-1-i), the
+ *               span's partial, its last block unmultiplied.
+ *   level       the partials are the blocks of the next level under
+ *               G = r^m: the SAME kernel runs over them (32-byte entries of
+ *               five limbs) until one is left.  Spans are aligned to the END
+ *               of the data; zero blocks in front change nothing.
+ *   finish      one wave: h = S r, for the AEAD h = (h + lengths) r, the full
+ *               reduction mod p, a constant-time conditional subtract, + s.
+ *
+ * Arithmetic: five 26-bit limbs, 2^130 = 5 (mod p).  A product limb is five
+ * 32x32->64 multiply-adds (v_mad_u64_u32) with precomputed 5 r_i.  Carry
+ * bound: operand limbs a_i < 2^28 (a carried value is < 2^26 + 2^13, a raw
+ * block limb < 2^26, block 0 adds the incoming state), multiplier limbs
+ * b_j < 2^27, 5 b_j < 2^29.33: one term < 2^57.33, the five of one
+ * multiplication < 2^59.66, so a 64-bit limb could overflow after 20
+ * accumulated multiplications.  The code carries after PL_BATCH = 4 (plus one
+ * added block): < 2^61.7.  The wave sum adds 64 carried limbs: < 2^33 in 64
+ * bits.  The multipliers of a Horner step are wave-uniform (SGPRs); the powers
+ * of r are computed on the host, which knows r, and travel by value: no
+ * setup kernel, no host synchronisation.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "otc_device.h"
+#include "otc_kernels.h"
+
+namespace otc_impl {
+
+using otc_dev::alloc_fault;
+using otc_dev::lane_id;
+using otc_dev::ld_u4;
+using otc_dev::st_u4;
+
+namespace {
+
+/* ======================= ChaCha20 ========================================= */
+
+constexpr uint32_t CC_WAVES = 4;        /* waves of a workgroup */
+constexpr uint32_t CC_RUN = 4;          /* passes of a wave */
+constexpr uint32_t CC_PASS = 64 * 64;   /* bytes of a pass */
+
+struct CcParams {
+    uint32_t key[8], nonce[3], ctr0;
+    const uint8_t *in;
+    uint8_t *out;
+    uint64_t npass;  /* bulk: whole passes from byte 0 */
+    uint64_t off;    /* edge: its first byte (a multiple of 64) */
+    uint64_t nbytes; /* edge: bytes of the whole call */
+};
+
+/* rotations: 16 and 8 as byte permutes, 12 and 7 as v_alignbit_b32 */
+__device__ __forceinline__ uint32_t cc_rot16(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x01000302u); }
+__device__ __forceinline__ uint32_t cc_rot8(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x02010003u); }
+__device__ __forceinline__ uint32_t cc_rot12(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 20); }
+__device__ __forceinline__ uint32_t cc_rot7(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 25); }
+
+__device__ __forceinline__ void cc_qr(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d)
+{
+    a += b; d = cc_rot16(d ^ a);
+    c += d; b = cc_rot12(b ^ c);
+    a += b; d = cc_rot8(d ^ a);
+    c += d; b = cc_rot7(b ^ c);
+}
+
+/* the keystream block of counter `ctr` */
+__device__ __forceinline__ void cc_block(const CcParams &P, uint32_t ctr, uint32_t (&x)[16])
+{
+    const uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u,
+                            P.key[0], P.key[1], P.key[2], P.key[3], P.key[4], P.key[5], P.key[6], P.key[7],
+                            ctr, P.nonce[0], P.nonce[1], P.nonce[2]};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] = s[i];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        cc_qr(x[0], x[4], x[8], x[12]);
+        cc_qr(x[1], x[5], x[9], x[13]);
+        cc_qr(x[2], x[6], x[10], x[14]);
+        cc_qr(x[3], x[7], x[11], x[15]);
+        cc_qr(x[0], x[5], x[10], x[15]);
+        cc_qr(x[1], x[6], x[11], x[12]);
+        cc_qr(x[2], x[7], x[8], x[13]);
+        cc_qr(x[3], x[4], x[9], x[14]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] += s[i];
+}
+
+/* One butterfly of the 4x4 transpose among the lanes of a quad: with the
+ * partner lane q ^ D, exchange quarter e | D of the lane whose bit is clear
+ * with quarter e of the lane whose bit is set (hi). */
+template <int D>
+__device__ __forceinline__ void cc_xchg(uint32_t (&x)[16], bool hi)
+{
+    constexpr int ctrl = D == 1 ? 0xB1 /* quad_perm [1,0,3,2] */ : 0x4E /* [2,3,0,1] */;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e & D) continue;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            uint32_t &lo = x[4 * e + w], &up = x[4 * (e | D) + w];
+            const uint32_t send = hi ? lo : up;
+            const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp((int)send, (int)send, ctrl, 0xF, 0xF, false);
+            lo = hi ? recv : lo;
+            up = hi ? up : recv;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * CC_WAVES) void k_chacha20_bulk(CcParams P)
+{
+    const uint32_t lane = lane_id();
+    const uint64_t wave = (uint64_t)blockIdx.x * CC_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    /* lane 4g + q computes block 16q + g of the pass; its 16-byte piece j is at (64 j + lane) * 16 */
+    const uint32_t lb = (lane & 3u) << 4 | lane >> 2;
+    for (uint32_t k = 0; k < CC_RUN; ++k) {
+        const uint64_t pass = wave * CC_RUN + k;
+        if (pass >= P.npass) break; /* wave-uniform */
+        const uint8_t *src = P.in + pass * CC_PASS + lane * 16;
+        uint8_t *dst = P.out + pass * CC_PASS + lane * 16;
+        uint4 m[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[j] = ld_u4<true, true>(src + j * 1024);
+        uint32_t x[16];
+        /* the host refuses a call whose last counter passes 2^32 - 1: no wrap */
+        cc_block(P, P.ctr0 + (uint32_t)(pass * 64) + lb, x);
+        /* quarter j of this lane's block goes to lane 4g + j, which stores it as its piece q */
+        cc_xchg<1>(x, (lane & 1u) != 0);
+        cc_xchg<2>(x, (lane & 2u) != 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            st_u4<true, true>(dst + j * 1024, make_uint4(m[j].x ^ x[4 * j], m[j].y ^ x[4 * j + 1], m[j].z ^ x[4 * j + 2],
+                                                         m[j].w ^ x[4 * j + 3]));
+    }
+}
+
+/* one block per lane from byte P.off, byte by byte; touches nothing outside
+ * [in, in + nbytes) and [out, out + nbytes) */
+__global__ __launch_bounds__(256) void k_chacha20_edge(CcParams P)
+{
+    const uint64_t at = P.off + ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 64;
+    if (at >= P.nbytes) return;
+    const uint64_t left = P.nbytes - at;
+    const uint32_t m = left < 64 ? (uint32_t)left : 64u;
+    uint32_t x[16];
+    cc_block(P, P.ctr0 + (uint32_t)(at / 64), x);
+    auto src = (__attribute__((address_space(1))) const uint8_t *)(P.in + at);
+    auto dst = (__attribute__((address_space(1))) uint8_t *)(P.out + at);
+#pragma unroll
+    for (uint32_t i = 0; i < 64; ++i)
+        if (i < m) dst[i] = (uint8_t)(src[i] ^ (x[i >> 2] >> (8 * (i & 3))));
+}
+
+/* ======================= Poly1305 ========================================= */
+
+constexpr uint32_t PL_RUN = 32;              /* blocks per lane in a wave span */
+constexpr uint32_t PL_BATCH = 4;             /* passes per carry */
+constexpr uint32_t PL_SPAN = 64 * PL_RUN;    /* blocks of a wave span */
+constexpr uint32_t PL_WAVES = 4;             /* wave spans of a workgroup */
+constexpr int PL_MAX_LEVELS = 4;             /* 2048^4 blocks: more than any call has */
+constexpr uint32_t PL_ENTRY = 32;            /* bytes of a partial: five limbs, padded */
+constexpr uint32_t M26 = 0x3FFFFFFu;
+static_assert(PL_RUN % PL_BATCH == 0, "a wave span is whole batches");
+
+struct Fe {
+    uint32_t l[5]; /* value = sum l[i] 2^(26 i) */
+};
+struct Mul {
+    uint32_t r[5], s[4]; /* a multiplier's limbs and 5 * r[1..4] */
+};
+
+__host__ __device__ __forceinline__ Mul mul_of(const Fe &a)
+{
+    Mul m;
+    for (int i = 0; i < 5; ++i) m.r[i] = a.l[i];
+    for (int i = 0; i < 4; ++i) m.s[i] = a.l[i + 1] * 5u;
+    return m;
+}
+
+/* d += a . m, unreduced (five multiply-adds per limb) */
+__host__ __device__ __forceinline__ void fe_mac(uint64_t (&d)[5], const Fe &a, const Mul &m)
+{
+    const uint64_t a0 = a.l[0], a1 = a.l[1], a2 = a.l[2], a3 = a.l[3], a4 = a.l[4];
+    d[0] += a0 * m.r[0] + a1 * m.s[3] + a2 * m.s[2] + a3 * m.s[1] + a4 * m.s[0];
+    d[1] += a0 * m.r[1] + a1 * m.r[0] + a2 * m.s[3] + a3 * m.s[2] + a4 * m.s[1];
+    d[2] += a0 * m.r[2] + a1 * m.r[1] + a2 * m.r[0] + a3 * m.s[3] + a4 * m.s[2];
+    d[3] += a0 * m.r[3] + a1 * m.r[2] + a2 * m.r[1] + a3 * m.r[0] + a4 * m.s[3];
+    d[4] += a0 * m.r[4] + a1 * m.r[3] + a2 * m.r[2] + a3 * m.r[1] + a4 * m.r[0];
+}
+
+/* one carry chain: limbs 0, 2, 3, 4 below 2^26, limb 1 below 2^26 + 2^13 */
+__host__ __device__ __forceinline__ Fe fe_carry(uint64_t (&d)[5])
+{
+    d[1] += d[0] >> 26;
+    d[2] += d[1] >> 26;
+    d[3] += d[2] >> 26;
+    d[4] += d[3] >> 26;
+    const uint64_t t = (d[0] & M26) + (d[4] >> 26) * 5; /* 2^130 = 5 */
+    Fe f;
+    f.l[0] = (uint32_t)t & M26;
+    f.l[1] = (uint32_t)((d[1] & M26) + (t >> 26));
+    f.l[2] = (uint32_t)d[2] & M26;
+    f.l[3] = (uint32_t)d[3] & M26;
+    f.l[4] = (uint32_t)d[4] & M26;
+    return f;
+}
+
+__host__ __device__ __forceinline__ Fe fe_mul(const Fe &a, const Mul &m)
+{
+    uint64_t d[5] = {0, 0, 0, 0, 0};
+    fe_mac(d, a, m);
+    return fe_carry(d);
+}
+
+/* a 16-byte block (little-endian words) plus hibit * 2^128 */
+__host__ __device__ __forceinline__ Fe fe_of_words(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t hibit)
+{
+    Fe f;
+    f.l[0] = w0 & M26;
+    f.l[1] = (w0 >> 26 | w1 << 6) & M26;
+    f.l[2] = (w1 >> 20 | w2 << 12) & M26;
+    f.l[3] = (w2 >> 14 | w3 << 18) & M26;
+    f.l[4] = w3 >> 8 | hibit << 24;
+    return f;
+}
+
+struct PlLevel {
+    const uint8_t *in;  /* level 0: the message, 16-byte aligned; above: PL_ENTRY-byte partials */
+    uint64_t nbytes;    /* level 0: bytes of the message */
+    uint64_t nblocks;   /* blocks (entries) of this level, >= 1 */
+    uint64_t nspans;    /* ceil(nblocks / PL_SPAN) */
+    uint64_t pad;       /* nspans * PL_SPAN - nblocks zero blocks in front */
+    uint32_t *out;      /* nspans partials */
+    Fe y0;              /* level 0: the incoming state, added to block 0 */
+    uint32_t pad16;     /* level 0: a short last block is zero-padded to a full one (the AEAD's pad16),
+                           else it gets the 0x01 byte */
+    Mul m[PL_BATCH];    /* C^64, C^128, C^192, C^256 for this level's C */
+    Fe pw[64];          /* C^0 .. C^63 */
+};
+
+/* block i of the level; never reads at or past in + nbytes */
+template <bool RAW>
+__device__ __forceinline__ Fe pl_load(const PlLevel &P, uint64_t i)
+{
+    if constexpr (!RAW) {
+        const uint4 a = ld_u4<false, true>(P.in + i * PL_ENTRY), b = ld_u4<false, true>(P.in + i * PL_ENTRY + 16);
+        Fe f;
+        f.l[0] = a.x, f.l[1] = a.y, f.l[2] = a.z, f.l[3] = a.w, f.l[4] = b.x;
+        return f;
+    } else {
+        const uint64_t off = i * 16;
+        uint32_t w[4] = {0, 0, 0, 0}, hibit = 1;
+        if (off + 16 <= P.nbytes) {
+            const uint4 x = ld_u4<true, true>(P.in + off);
+            w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
+        } else {
+            /* the short last block: a branch on the length, never on the data */
+            const uint32_t n = (uint32_t)(P.nbytes - off);
+            auto src = (__attribute__((address_space(1))) const uint8_t *)(P.in + off);
+#pragma unroll
+            for (uint32_t b = 0; b < 15; ++b)
+                if (b < n) w[b >> 2] |= (uint32_t)src[b] << (8 * (b & 3));
+            if (!P.pad16) {
+                hibit = 0;
+#pragma unroll
+                for (uint32_t b = 1; b < 16; ++b)
+                    if (b == n) w[b >> 2] |= 1u << (8 * (b & 3));
+            }
+        }
+        Fe f = fe_of_words(w[0], w[1], w[2], w[3], hibit);
+        if (i == 0)
+            for (int k = 0; k < 5; ++k) f.l[k] += P.y0.l[k];
+        return f;
+    }
+}
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+template <bool RAW>
+__global__ __launch_bounds__(64 * PL_WAVES) void k_poly1305_level(PlLevel P)
+{
+    const uint32_t lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t ngroups = (P.nspans + PL_WAVES - 1) / PL_WAVES;
+    for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const uint64_t s = g * PL_WAVES + wave;
+        if (s >= P.nspans) break; /* wave-uniform; nothing in this kernel synchronises waves */
+        const uint64_t v0 = s * PL_SPAN; /* index among the zero-extended blocks */
+        /* the first span skips the batches that are all padding */
+        const uint32_t k0 = v0 < P.pad ? (uint32_t)((P.pad - v0) / 64) & ~(PL_BATCH - 1) : 0u;
+        Fe A = {{0, 0, 0, 0, 0}};
+        for (uint32_t kb = k0; kb < PL_RUN; kb += PL_BATCH) {
+            Fe X[PL_BATCH];
+#pragma unroll
+            for (uint32_t i = 0; i < PL_BATCH; ++i) {
+                const uint64_t v = v0 + (uint64_t)(kb + i) * 64 + lane;
+                if (v >= P.pad)
+                    X[i] = pl_load<RAW>(P, v - P.pad);
+                else
+                    X[i] = Fe{{0, 0, 0, 0, 0}};
+            }
+            uint64_t d[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) d[k] = X[PL_BATCH - 1].l[k];
+            fe_mac(d, A, P.m[PL_BATCH - 1]);
+#pragma unroll
+            for (uint32_t i = 0; i + 1 < PL_BATCH; ++i) fe_mac(d, X[i], P.m[PL_BATCH - 2 - i]);
+            A = fe_carry(d);
+        }
+        /* fold: lane j's blocks are 63 - j short of the span's last */
+        uint64_t d[5] = {0, 0, 0, 0, 0};
+        fe_mac(d, A, mul_of(P.pw[63 - lane]));
+        A = fe_carry(d);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) d[k] = wave_sum(A.l[k]);
+        A = fe_carry(d);
+        if (lane == 0) {
+            st_u4<false, true>(P.out + s * (PL_ENTRY / 4), make_uint4(A.l[0], A.l[1], A.l[2], A.l[3]));
+            st_u4<false, true>(P.out + s * (PL_ENTRY / 4) + 4, make_uint4(A.l[4], 0, 0, 0));
+        }
+    }
+}
+
+struct PlFinal {
+    const uint32_t *s; /* the last level's one partial; null: no data, h = y0 */
+    Fe y0;
+    Mul r;
+    Fe len;            /* the AEAD's length block with its 2^128 bit */
+    uint32_t aead;     /* 1: h = (h + len) r before the reduction */
+    uint32_t skey[4];  /* s, little-endian words */
+    uint32_t *out;     /* 16 bytes */
+};
+
+__global__ __launch_bounds__(64) void k_poly1305_final(PlFinal F)
+{
+    Fe h = F.y0;
+    if (F.s) { /* on the call's shape, not on data */
+        Fe p;
+        for (int k = 0; k < 5; ++k) p.l[k] = F.s[k];
+        h = fe_mul(p, F.r);
+    }
+    if (F.aead) {
+        for (int k = 0; k < 5; ++k) h.l[k] += F.len.l[k];
+        h = fe_mul(h, F.r);
+    }
+    /* the full reduction: two carry chains bring h below 2^130 with every limb below 2^26 ... */
+    uint32_t h0 = h.l[0], h1 = h.l[1], h2 = h.l[2], h3 = h.l[3], h4 = h.l[4], c;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        c = h0 >> 26; h0 &= M26; h1 += c;
+        c = h1 >> 26; h1 &= M26; h2 += c;
+        c = h2 >> 26; h2 &= M26; h3 += c;
+        c = h3 >> 26; h3 &= M26; h4 += c;
+        c = h4 >> 26; h4 &= M26; h0 += c * 5;
+    }
+    c = h0 >> 26; h0 &= M26; h1 += c;
+    /* ... then g = h - p = h + 5 - 2^130, taken by a mask where it did not borrow: no branch on the value */
+    uint32_t g0 = h0 + 5;
+    c = g0 >> 26; g0 &= M26;
+    uint32_t g1 = h1 + c;
+    c = g1 >> 26; g1 &= M26;
+    uint32_t g2 = h2 + c;
+    c = g2 >> 26; g2 &= M26;
+    uint32_t g3 = h3 + c;
+    c = g3 >> 26; g3 &= M26;
+    const uint32_t g4 = h4 + c - (1u << 26);
+    const uint32_t take = (g4 >> 31) - 1u; /* all ones iff h >= p */
+    h0 = (h0 & ~take) | (g0 & take);
+    h1 = (h1 & ~take) | (g1 & take);
+    h2 = (h2 & ~take) | (g2 & take);
+    h3 = (h3 & ~take) | (g3 & take);
+    h4 = (h4 & ~take) | (g4 & take);
+    /* h mod 2^128, plus s mod 2^128 */
+    const uint32_t w0 = h0 | h1 << 26, w1 = h1 >> 6 | h2 << 20, w2 = h2 >> 12 | h3 << 14, w3 = h3 >> 18 | h4 << 8;
+    uint64_t f = (uint64_t)w0 + F.skey[0];
+    const uint32_t t0 = (uint32_t)f;
+    f = (uint64_t)w1 + F.skey[1] + (f >> 32);
+    const uint32_t t1 = (uint32_t)f;
+    f = (uint64_t)w2 + F.skey[2] + (f >> 32);
+    const uint32_t t2 = (uint32_t)f;
+    f = (uint64_t)w3 + F.skey[3] + (f >> 32);
+    const uint32_t t3 = (uint32_t)f;
+    const uint32_t l = threadIdx.x;
+    /* lanes 0..3 store one word each */
+    if (l < 4) F.out[l] = l == 0 ? t0 : l == 1 ? t1 : l == 2 ? t2 : t3;
+}
+
+uint32_t ld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+/* blocks and spans of every level over nbytes of data */
+struct PlPlan {
+    int nlevels;
+    uint64_t nblocks[PL_MAX_LEVELS], nspans[PL_MAX_LEVELS];
+    size_t bytes; /* every level's partials */
+};
+bool pl_plan(uint64_t nbytes, PlPlan &pl)
+{
+    pl.nlevels = 0;
+    pl.bytes = 0;
+    if (nbytes > UINT64_MAX - 15) return false;
+    uint64_t n = (nbytes + 15) / 16;
+    while (n) {
+        if (pl.nlevels == PL_MAX_LEVELS) return false;
+        const uint64_t sp = (n + PL_SPAN - 1) / PL_SPAN;
+        pl.nblocks[pl.nlevels] = n;
+        pl.nspans[pl.nlevels] = sp;
+        pl.bytes += (size_t)sp * PL_ENTRY;
+        ++pl.nlevels;
+        n = sp > 1 ? sp : 0;
+    }
+    return true;
+}
+
+} // namespace
+
+/* ---- host entry points ---------------------------------------------------- */
+
+hipError_t chacha20_run(const void *in, void *out, uint64_t nbytes, const uint8_t key[32], const uint8_t nonce[12],
+                        uint32_t counter, hipStream_t st)
+{
+    if (nbytes == 0) return hipSuccess;
+    CcParams P{};
+    for (int i = 0; i < 8; ++i) P.key[i] = ld32(key + 4 * i);
+    for (int i = 0; i < 3; ++i) P.nonce[i] = ld32(nonce + 4 * i);
+    P.ctr0 = counter;
+    P.in = (const uint8_t *)in;
+    P.out = (uint8_t *)out;
+    P.nbytes = nbytes;
+    const bool aligned = !(((uintptr_t)in | (uintptr_t)out) & 15u);
+    P.npass = aligned ? nbytes / CC_PASS : 0;
+    P.off = P.npass * CC_PASS;
+    if (P.npass) {
+        const uint64_t per = (uint64_t)CC_WAVES * CC_RUN, wgs = (P.npass + per - 1) / per;
+        if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_chacha20_bulk, dim3((unsigned)wgs), dim3(64 * CC_WAVES), 0, st, P);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (P.off < nbytes) {
+        const uint64_t blocks = (nbytes - P.off + 63) / 64, wgs = (blocks + 255) / 256;
+        if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_chacha20_edge, dim3((unsigned)wgs), dim3(256), 0, st, P);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+int poly1305_spans(uint64_t *spans, int max)
+{
+    const uint64_t all[] = {64 * 16ull,                           /* a pass */
+                            PL_BATCH * 64 * 16ull,                /* a batch of passes */
+                            PL_SPAN * 16ull,                      /* a wave span */
+                            (uint64_t)PL_WAVES * PL_SPAN * 16,    /* a workgroup's spans */
+                            (uint64_t)PL_SPAN * PL_SPAN * 16,     /* a level-2 span */
+                            (uint64_t)PL_SPAN * PL_SPAN * PL_SPAN * 16};
+    const int n = (int)(sizeof all / sizeof all[0]);
+    for (int i = 0; i < n && i < max; ++i) spans[i] = all[i];
+    return n;
+}
+
+hipError_t poly1305_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws)
+{
+    *ws = nullptr;
+    PlPlan pl;
+    if (!pl_plan(nbytes, pl)) return hipErrorInvalidValue;
+    if (pl.nlevels == 0) return hipSuccess;
+    if (alloc_fault()) return hipErrorOutOfMemory;
+    return hipMallocAsync(ws, pl.bytes, st);
+}
+
+hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], const uint32_t h0[5],
+                        const uint8_t s[16], const uint8_t *lenblock, bool pad16, void *out16, void *ws,
+                        hipStream_t st)
+{
+    PlPlan pl;
+    if (!pl_plan(nbytes, pl) || (pl.nlevels && !ws)) {
+        if (ws) (void)hipFreeAsync(ws, st);
+        return hipErrorInvalidValue;
+    }
+    Fe R, Y0;
+    for (int k = 0; k < 5; ++k) R.l[k] = r[k], Y0.l[k] = h0[k];
+    PlFinal F{};
+    F.s = nullptr;
+    F.y0 = Y0;
+    F.r = mul_of(R);
+    F.aead = lenblock ? 1u : 0u;
+    if (lenblock) F.len = fe_of_words(ld32(lenblock), ld32(lenblock + 4), ld32(lenblock + 8), ld32(lenblock + 12), 1);
+    for (int i = 0; i < 4; ++i) F.skey[i] = ld32(s + 4 * i);
+    F.out = (uint32_t *)out16;
+    hipError_t e = hipSuccess;
+    const uint8_t *in = (const uint8_t *)data;
+    uint32_t *part = (uint32_t *)ws;
+    Fe C = R; /* level l works under C = r^(PL_SPAN^l) */
+    for (int l = 0; l < pl.nlevels && e == hipSuccess; ++l) {
+        PlLevel P{};
+        P.in = in;
+        P.nbytes = l == 0 ? nbytes : 0;
+        P.nblocks = pl.nblocks[l];
+        P.nspans = pl.nspans[l];
+        P.pad = P.nspans * PL_SPAN - P.nblocks;
+        P.out = part;
+        P.y0 = l == 0 ? Y0 : Fe{{0, 0, 0, 0, 0}};
+        P.pad16 = pad16 ? 1u : 0u;
+        const Mul mc = mul_of(C);
+        P.pw[0] = Fe{{1, 0, 0, 0, 0}};
+        for (int j = 1; j < 64; ++j) P.pw[j] = fe_mul(P.pw[j - 1], mc);
+        const Fe c64 = fe_mul(P.pw[63], mc);
+        const Mul m64 = mul_of(c64);
+        Fe p = c64;
+        for (uint32_t k = 0; k < PL_BATCH; ++k) {
+            P.m[k] = mul_of(p);
+            if (k + 1 < PL_BATCH) p = fe_mul(p, m64);
+        }
+        /* C^(64 PL_BATCH), squared on to C^PL_SPAN */
+        for (uint32_t q = 64 * PL_BATCH; q < PL_SPAN; q *= 2) p = fe_mul(p, mul_of(p));
+        C = p;
+        const uint64_t ngroups = (P.nspans + PL_WAVES - 1) / PL_WAVES, cap = (uint64_t)otc_dev::device_cus() * 16;
+        const dim3 g((unsigned)(ngroups < cap ? ngroups : cap)), b(64 * PL_WAVES);
+        if (l == 0)
+            hipLaunchKernelGGL(k_poly1305_level<true>, g, b, 0, st, P); /* the data streams once */
+        else
+            hipLaunchKernelGGL(k_poly1305_level<false>, g, b, 0, st, P); /* partials come back from L2 */
+        e = hipGetLastError();
+        in = (const uint8_t *)part;
+        F.s = part;
+        part += P.nspans * (PL_ENTRY / 4);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_poly1305_final, dim3(1), dim3(64), 0, st, F);
+        e = hipGetLastError();
+    }
+    if (ws) {
+        const hipError_t f = hipFreeAsync(ws, st);
+        if (e == hipSuccess) e = f;
+    }
+    return e;
+}
+
+} // namespace otc_impl

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "aes.h"
+#include "chacha.h"
 #include "otc.h"
 #include "otc_aesni.h"
 #include "otc_device.h"
@@ -654,6 +655,118 @@ extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_g
     e = otc_impl::ghash_run(dir == OTC_DIR_ENCRYPT ? out : in, nbytes, k->h, y0, lenblock, ekj0, tag_dev, ws, st);
     if (e != hipSuccess) return hip_fail(e, "gcm hash launch");
     if (dir == OTC_DIR_DECRYPT && nbytes) return ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream);
+    return OTC_OK;
+}
+
+/* ---- ChaCha20, Poly1305, ChaCha20-Poly1305 (RFC 8439) ---------------------- */
+/* what every ChaCha20 call checks before anything is launched: the buffers
+ * (any alignment; the same buffer or disjoint) and the 32-bit block counter,
+ * which this engine never lets wrap */
+static int chacha_check(const void *in, const void *out, size_t nbytes, uint32_t counter, const char *what)
+{
+    const uint64_t nblk = (uint64_t)nbytes / 64 + (nbytes % 64 ? 1 : 0);
+    if ((uint64_t)counter + nblk > ((uint64_t)1 << 32))
+        return set_err(OTC_ERR_ARG, std::string(what) + ": the 32-bit block counter would pass 2^32 - 1");
+    if (nbytes == 0) return OTC_OK;
+    if (!in || !out) return set_err(OTC_ERR_ARG, std::string(what) + ": null buffer");
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    if (a != b && a < b + nbytes && b < a + nbytes)
+        return set_err(OTC_ERR_ARG, std::string(what) + ": input and output overlap partially");
+    return OTC_OK;
+}
+
+extern "C" int otc_chacha20(const void *in, void *out, size_t nbytes, const uint8_t key[32], const uint8_t nonce[12],
+                            uint32_t counter, void *stream)
+{
+    Range rg("otc_chacha20");
+    if (!key || !nonce) return set_err(OTC_ERR_ARG, "chacha20: null key or nonce");
+    if (int r = chacha_check(in, out, nbytes, counter, "chacha20")) return r;
+    const hipError_t e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, counter, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "chacha20 launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_poly1305_spans(uint64_t *spans, int max)
+{
+    uint64_t none;
+    return otc_impl::poly1305_spans(spans ? spans : &none, spans ? max : 0);
+}
+
+/* the hash over device data from a host-side state: workspace first, then the kernels */
+static int poly1305_dev(const void *data, size_t nbytes, const poly1305_state &ps, const uint8_t *lenblock, bool pad16,
+                        void *tag_dev, void *ws, hipStream_t st, const char *what)
+{
+    const hipError_t e = otc_impl::poly1305_run(data, nbytes, ps.r, ps.h, ps.s, lenblock, pad16, tag_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return OTC_OK;
+}
+
+static int poly1305_ws(size_t nbytes, hipStream_t st, void **ws, const char *what)
+{
+    const hipError_t e = otc_impl::poly1305_ws_alloc(nbytes, st, ws);
+    if (e == hipSuccess) return OTC_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return set_err(OTC_ERR_NOMEM, std::string(what) + ": no memory for the hash's partials");
+    if (e == hipErrorInvalidValue) return set_err(OTC_ERR_ARG, std::string(what) + ": too many bytes");
+    return hip_fail(e, what);
+}
+
+extern "C" int otc_poly1305(const void *data, size_t nbytes, const uint8_t key[32], void *tag_dev, void *stream)
+{
+    Range rg("otc_poly1305");
+    if (!key || !tag_dev) return set_err(OTC_ERR_ARG, "poly1305: null argument");
+    if ((uintptr_t)tag_dev & 3u) return set_err(OTC_ERR_ARG, "poly1305: the tag must be 4-byte aligned");
+    if (nbytes && !data) return set_err(OTC_ERR_ARG, "poly1305: null buffer");
+    if (nbytes && ((uintptr_t)data & 15u)) return set_err(OTC_ERR_ARG, "poly1305: device buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    poly1305_state ps;
+    poly1305_init(&ps, key);
+    void *ws = nullptr;
+    if (int r = poly1305_ws(nbytes, st, &ws, "poly1305")) return r;
+    return poly1305_dev(data, nbytes, ps, nullptr, false, tag_dev, ws, st, "poly1305 launch");
+}
+
+extern "C" int otc_chacha20_poly1305(const void *in, void *out, size_t nbytes, const uint8_t key[32], int dir,
+                                     const uint8_t nonce[12], const uint8_t *aad, size_t aad_len, void *tag_dev,
+                                     void *stream)
+{
+    Range rg("otc_chacha20_poly1305");
+    if (!key || !nonce) return set_err(OTC_ERR_ARG, "chacha20_poly1305: null key or nonce");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (aad_len && !aad) return set_err(OTC_ERR_ARG, "chacha20_poly1305: null aad");
+    if (!tag_dev || ((uintptr_t)tag_dev & 3u))
+        return set_err(OTC_ERR_ARG, "chacha20_poly1305: the tag must be 4-byte aligned device memory");
+    if ((uint64_t)nbytes > CHACHA20_POLY1305_MAX_BYTES)
+        return set_err(OTC_ERR_ARG, "chacha20_poly1305: a message has at most (2^32 - 1) * 64 bytes");
+    if (int r = check_bufs(in, out, nbytes, true, "chacha20_poly1305")) return r;
+    hipStream_t st = (hipStream_t)stream;
+
+    /* what does not depend on the data, on the host: the one-time key (block
+     * 0), the hash state after the AAD, the length block */
+    uint8_t b0[64], lenblock[16];
+    chacha20_block(key, nonce, 0, b0);
+    poly1305_state ps;
+    poly1305_init(&ps, b0);
+    poly1305_pad16(&ps, aad, aad_len);
+    for (int i = 0; i < 8; ++i) {
+        lenblock[i] = (uint8_t)((uint64_t)aad_len >> (8 * i));
+        lenblock[8 + i] = (uint8_t)((uint64_t)nbytes >> (8 * i));
+    }
+
+    /* the hash's memory first: a failure leaves out and the tag untouched */
+    void *ws = nullptr;
+    if (int r = poly1305_ws(nbytes, st, &ws, "chacha20_poly1305")) return r;
+    hipError_t e;
+    if (dir == OTC_DIR_ENCRYPT && (e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, 1, st)) != hipSuccess) {
+        if (ws) (void)hipFreeAsync(ws, st);
+        return hip_fail(e, "chacha20_poly1305 cipher launch");
+    }
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    if (int r = poly1305_dev(dir == OTC_DIR_ENCRYPT ? out : in, nbytes, ps, lenblock, true, tag_dev, ws, st,
+                             "chacha20_poly1305 hash launch"))
+        return r;
+    if (dir == OTC_DIR_DECRYPT && (e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, 1, st)) != hipSuccess)
+        return hip_fail(e, "chacha20_poly1305 cipher launch");
     return OTC_OK;
 }
 

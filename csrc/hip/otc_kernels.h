@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, stream_ops.hip), declared once: included by their callers
+ * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip, stream_ops.hip), declared once: included by their callers
  * (engine.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
  * of the public C API (otc.h).
@@ -130,6 +130,26 @@ hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K
 hipError_t bs_claim(const Job &j, SplitClaim cl, hipStream_t st);
 hipError_t bs_preload();
 int strace_read_bs(unsigned long long *buf, int max);
+
+/* ---- chacha.hip ---------------------------------------------------------- */
+/* out = in ^ ChaCha20 keystream (RFC 8439 layout) from block `counter`; any
+ * byte count and alignment; the caller has checked that the counter does not
+ * pass 2^32 - 1 */
+hipError_t chacha20_run(const void *in, void *out, uint64_t nbytes, const uint8_t key[32], const uint8_t nonce[12],
+                        uint32_t counter, hipStream_t st);
+/* byte sizes of the Poly1305 decomposition's pieces, smallest first; returns how many there are */
+int poly1305_spans(uint64_t *spans, int max);
+/* the per-call partials of poly1305_run over nbytes, stream-ordered (behind
+ * otc_fault_inject_alloc); *ws stays null for nbytes == 0 */
+hipError_t poly1305_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws);
+/* out16 (device) = Poly1305 under the clamped r (five 26-bit limbs) and s,
+ * continued from the state h0 (limbs) over nbytes of 16-byte aligned device
+ * data.  lenblock: the AEAD's 16-byte length block, hashed last.  pad16: a
+ * short last block is zero-padded to a full one (the AEAD), else it gets the
+ * 0x01 byte.  Frees ws behind its kernels, also when it fails. */
+hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], const uint32_t h0[5],
+                        const uint8_t s[16], const uint8_t *lenblock, bool pad16, void *out16, void *ws,
+                        hipStream_t st);
 
 /* ---- stream_ops.hip ------------------------------------------------------ */
 hipError_t k_xor(const void *a, const void *b, void *out, size_t n, hipStream_t st);

@@ -252,6 +252,47 @@ int otc_ghash(const void *data, size_t nbytes, const uint8_t h[16], const uint8_
  * kernel takes another path.  Writes up to max of them; returns the count. */
 int otc_ghash_spans(uint64_t *spans, int max);
 
+/* ---- ChaCha20, Poly1305, ChaCha20-Poly1305 (RFC 8439) ----------------------
+ * The IETF layout: a 32-byte key, a 12-byte nonce, a 32-bit block counter
+ * (state word 12).  key, nonce and aad are HOST memory; the data is device
+ * memory; calls are asynchronous on the caller's stream, do not synchronise
+ * and can be captured in a graph.  One kernel family (csrc/hip/chacha.hip):
+ * otc_last_impl and otc_pick_impl do not know these modes.
+ *
+ * Counter wrap: RFC 8439 leaves an overflow of the 32-bit counter undefined
+ * and implementations differ (some carry into the first nonce word, some wrap
+ * to 0 and repeat keystream).  This engine refuses: a call with
+ * counter + ceil(nbytes / 64) > 2^32 returns OTC_ERR_ARG before any HIP call;
+ * a call whose last block is exactly 2^32 - 1 is fine.
+ *
+ * otc_chacha20: out = in ^ keystream from block `counter`.  Any byte count,
+ * any alignment (buffers that are not both 16-byte aligned run on the
+ * byte-wise edge kernel, which is slower); in == out or disjoint. */
+int otc_chacha20(const void *in, void *out, size_t nbytes, const uint8_t key[32], const uint8_t nonce[12],
+                 uint32_t counter, void *stream);
+/* tag_dev[16] (device, 4-byte aligned) = Poly1305 of nbytes of device data
+ * (16-byte aligned) under the one-time key r || s (r is clamped here).
+ * Parallel over the whole chip; its partials are one stream-ordered
+ * allocation made before anything is launched (OTC_ERR_NOMEM leaves tag_dev
+ * untouched; otc_fault_inject_alloc covers it). */
+int otc_poly1305(const void *data, size_t nbytes, const uint8_t key[32], void *tag_dev, void *stream);
+/* Byte sizes of the pieces the Poly1305 kernel cuts its data into, smallest
+ * first (a pass of 64 lanes, a batch of passes, a wave's span, a workgroup's
+ * spans, a level-2 span, a level-3 span), like otc_ghash_spans. */
+int otc_poly1305_spans(uint64_t *spans, int max);
+/* The AEAD of RFC 8439 section 2.8 over ONE message in device memory: nbytes
+ * is 0 .. (2^32 - 1) * 64, buffers 16-byte aligned.  The one-time Poly1305
+ * key (block 0), the hash state after the AAD and the length block are
+ * computed on the host and travel by value.  tag_dev receives the COMPUTED
+ * tag in both directions (comparing it is the caller's, as with otc_aes_gcm).
+ * Stream order: encrypt: ChaCha20 from counter 1, then Poly1305 over out;
+ * decrypt: Poly1305 over in, then ChaCha20 -- in place works both ways.
+ * nbytes == 0 launches only the hash's finishing kernel.  The workspace is
+ * allocated before anything is launched: OTC_ERR_NOMEM leaves out and tag_dev
+ * untouched. */
+int otc_chacha20_poly1305(const void *in, void *out, size_t nbytes, const uint8_t key[32], int dir,
+                          const uint8_t nonce[12], const uint8_t *aad, size_t aad_len, void *tag_dev, void *stream);
+
 /* CFB128 decryption (parallel): P_i = C_i ^ E(C_{i-1}), C_{-1} = iv;
  * nbytes % 16 == 0; encryption key.  _impl: with a kernel choice (the plain
  * form is OTC_IMPL_AUTO: the T-table + bitsliced split from 2 GiB, the

@@ -167,6 +167,12 @@ def _declare_cpu(lib):
         "aes_crypt_ctr32": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_crypt_gcm": (c_int, [P(AesGcmContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_gcm_auth_decrypt": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
+        "chacha20_block": (None, [c_u8p, c_u8p, ctypes.c_uint32, c_u8p]),
+        "chacha20_crypt": (c_int, [c_u8p, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_sz]),
+        "poly1305_mac": (None, [c_u8p, c_u8p, c_sz, c_u8p]),
+        "chacha20_poly1305_encrypt": (c_int, [c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_sz, c_u8p]),
+        "chacha20_poly1305_auth_decrypt": (c_int, [c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_sz]),
+        "chacha20_poly1305_tag": (c_int, [c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_sz, c_u8p]),
         "arc4_setup": (None, [P(Arc4Context), c_u8p, ctypes.c_uint]),
         "arc4_prep": (c_int, [P(Arc4Context), c_sz, c_u8p]),
         "arc4_crypt": (c_int, [c_sz, c_u8p, c_u8p, c_u8p]),
@@ -233,6 +239,10 @@ def _declare_gpu(lib):
         "otc_ghash_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
         "otc_aes_gcm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u64, c_int, c_sz, P(OtcGcmKey), c_vp, c_vp, c_int,
                                       c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
+        "otc_chacha20": (c_int, [c_vp, c_vp, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_vp]),
+        "otc_poly1305": (c_int, [c_vp, c_sz, c_u8p, c_vp, c_vp]),
+        "otc_poly1305_spans": (c_int, [P(c_u64), c_int]),
+        "otc_chacha20_poly1305": (c_int, [c_vp, c_vp, c_sz, c_u8p, c_int, c_u8p, c_u8p, c_sz, c_vp, c_vp]),
         "otc_split_stats": (None, [c_int]),
         "otc_split_fallback_reason": (ctypes.c_char_p, []),
         "otc_split_last_units": (c_int, [ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]),

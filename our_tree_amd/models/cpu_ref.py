@@ -239,6 +239,97 @@ def gcm_auth_decrypt(key: bytes, iv: bytes, data: bytes, tag: bytes, aad: bytes 
     return bytes(out)[: len(data)]
 
 
+CHACHA_MAX_BYTES = ((1 << 32) - 1) * 64  # chacha.h CHACHA20_POLY1305_MAX_BYTES
+
+
+class ChaChaTagError(ValueError):
+    """The tag of a ChaCha20-Poly1305 message did not match; the plaintext was zeroed."""
+
+
+def _chacha_args(key, nonce):
+    key, nonce = bytes(key), bytes(nonce)
+    if len(key) != 32:
+        raise ValueError("a ChaCha20 key has 32 bytes")
+    if len(nonce) != 12:
+        raise ValueError("a ChaCha20 nonce has 12 bytes (RFC 8439)")
+    return key, nonce
+
+
+def chacha_check_counter(counter: int, nbytes: int) -> int:
+    """The 32-bit block counter of a call over ``nbytes``: RFC 8439 leaves its
+    overflow undefined, and this engine refuses a call whose last block would
+    pass 2**32 - 1 (the last block may be exactly that)."""
+    counter = int(counter)
+    if not 0 <= counter < 1 << 32:
+        raise ValueError("the ChaCha20 block counter is 0 .. 2**32 - 1")
+    if counter + (nbytes + 63) // 64 > 1 << 32:
+        raise ValueError("the ChaCha20 block counter would pass 2**32 - 1 (the 32-bit counter never wraps here)")
+    return counter
+
+
+def chacha20(key: bytes, nonce: bytes, data: bytes, counter: int = 0) -> bytes:
+    """ChaCha20 (RFC 8439: 32-byte key, 12-byte nonce, 32-bit block counter)
+    over any byte count, from block ``counter``."""
+    key, nonce = _chacha_args(key, nonce)
+    data = bytes(data)
+    counter = chacha_check_counter(counter, len(data))
+    out = _buf(len(data))
+    if _native.cpu_lib().chacha20_crypt(_native.as_u8p(key), _native.as_u8p(nonce), counter, _native.as_u8p(data), out,
+                                        len(data)):
+        raise ValueError("the ChaCha20 block counter would pass 2**32 - 1")
+    return bytes(out)[: len(data)]
+
+
+def poly1305(key: bytes, data: bytes) -> bytes:
+    """The 16-byte Poly1305 tag of ``data`` under the 32-byte one-time key r || s."""
+    key, data = bytes(key), bytes(data)
+    if len(key) != 32:
+        raise ValueError("a Poly1305 key has 32 bytes")
+    tag = _buf(16)
+    _native.cpu_lib().poly1305_mac(_native.as_u8p(key), _native.as_u8p(data), len(data), tag)
+    return bytes(tag)
+
+
+def chacha20_poly1305(key: bytes, nonce: bytes, data: bytes, aad: bytes = b"", decrypt: bool = False):
+    """ChaCha20-Poly1305 (RFC 8439 section 2.8) of one message: ``(out, tag)``
+    with the COMPUTED 16-byte tag in both directions."""
+    key, nonce = _chacha_args(key, nonce)
+    data, aad = bytes(data), bytes(aad)
+    if len(data) > CHACHA_MAX_BYTES:
+        raise ValueError("a ChaCha20-Poly1305 message has at most (2**32 - 1) * 64 bytes")
+    lib = _native.cpu_lib()
+    out, tag = _buf(len(data)), _buf(16)
+    k, n, a, d = _native.as_u8p(key), _native.as_u8p(nonce), _native.as_u8p(aad), _native.as_u8p(data)
+    if decrypt:
+        rc = lib.chacha20_poly1305_tag(k, n, a, len(aad), d, len(data), tag) or lib.chacha20_crypt(k, n, 1, d, out, len(data))
+    else:
+        rc = lib.chacha20_poly1305_encrypt(k, n, a, len(aad), d, out, len(data), tag)
+    if rc:
+        raise ValueError("invalid ChaCha20-Poly1305 lengths")
+    return bytes(out)[: len(data)], bytes(tag)
+
+
+def chacha20_poly1305_auth_decrypt(key: bytes, nonce: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
+    """Authenticated decryption: compares the 16-byte tag in constant time and
+    raises ChaChaTagError (the C side zeroes its output) on a mismatch."""
+    key, nonce = _chacha_args(key, nonce)
+    data, aad, tag = bytes(data), bytes(aad), bytes(tag)
+    if len(tag) != 16:
+        raise ValueError("a ChaCha20-Poly1305 tag has 16 bytes")
+    # not zero to begin with: err.output shows what the C side left on a mismatch
+    out = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(b"\xa5" * max(len(data), 1))
+    rc = _native.cpu_lib().chacha20_poly1305_auth_decrypt(_native.as_u8p(key), _native.as_u8p(nonce), _native.as_u8p(aad),
+                                                         len(aad), _native.as_u8p(tag), _native.as_u8p(data), out,
+                                                         len(data))
+    if rc == -0x12:
+        err = ChaChaTagError("ChaCha20-Poly1305 tag mismatch")
+        err.output = bytes(out)[: len(data)]
+        raise err
+    if rc:
+        raise ValueError("invalid ChaCha20-Poly1305 lengths")
+    return bytes(out)[: len(data)]
+
+
 def serial_encrypt(mode: str, key: bytes, iv: bytes, data: bytes) -> bytes:
     """Exact single-stream CBC / CFB128 encryption on one core with AES-NI
     (the C oracle where AES-NI is absent).  This is the host path for the

@@ -5,6 +5,8 @@ from .aes_ops import (IMPLS, CtrBatch, CtrStream, cbc_decrypt, cbc_decrypt_segme
                       split_fallback_reason, xts_decrypt, xts_encrypt,
                       GcmTagError, ctr32, gcm_decrypt, gcm_encrypt, ghash, ghash_spans,
                       GcmBatch, gcm_batch_spans, gcm_decrypt_batch, gcm_encrypt_batch, ghash_batch)
+from .chacha_ops import (ChaChaTagError, chacha20, chacha20_poly1305_decrypt, chacha20_poly1305_encrypt, poly1305,
+                         poly1305_spans)
 from .keys import expand_key
 from .stream_ops import checksum, clock_ghz, clock_probe, fill_random_, rc4_crypt_batch, rc4_multi, rc4_states, xor
 
@@ -15,4 +17,5 @@ __all__ = [
     "xts_encrypt", "xts_decrypt",
     "ctr32", "ghash", "ghash_spans", "gcm_encrypt", "gcm_decrypt", "GcmTagError",
     "GcmBatch", "gcm_encrypt_batch", "gcm_decrypt_batch", "ghash_batch", "gcm_batch_spans",
+    "chacha20", "poly1305", "poly1305_spans", "chacha20_poly1305_encrypt", "chacha20_poly1305_decrypt", "ChaChaTagError",
 ]

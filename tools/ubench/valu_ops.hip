@@ -4,7 +4,8 @@
 // wave at 4 waves per SIMD (the whole chip), so latency is hidden and the
 // time measures issue cost.  Printed: ns per launch and the cost relative to
 // v_xor_b32 (1.0 = same issue rate).  Question it answers: which transpose /
-// linear-layer forms are cheaper than their instruction count suggests.
+// linear-layer forms are cheaper than their instruction count suggests; and
+// what ChaCha20's adds and Poly1305's v_mad_u64_u32 cost beside them.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -23,12 +24,14 @@ enum {
     OP_PERMLANE32,
     OP_PERMLANE16,
     OP_XOR_DPP,
+    OP_ADD,
+    OP_MAD_U64_U32,
     OP_N
 };
 static const char *names[OP_N] = {"v_xor_b32",        "v_bitop3_b32",      "v_bfi_b32",         "v_perm_b32",
                                   "v_lshlrev_b32",    "v_lshl_or_b32",     "v_alignbit_b32",    "v_and_or_b32",
                                   "v_lshlrev_b64",    "v_pk_mov_b32",      "v_permlane32_swap", "v_permlane16_swap",
-                                  "v_xor_b32_dpp_row_shr1"};
+                                  "v_xor_b32_dpp_row_shr1", "v_add_u32",        "v_mad_u64_u32"};
 
 template <int OP>
 __global__ __launch_bounds__(256) void k_op(unsigned *out, int iters)
@@ -66,6 +69,11 @@ __global__ __launch_bounds__(256) void k_op(unsigned *out, int iters)
                 }
                 if (OP == OP_XOR_DPP)
                     asm volatile("v_xor_b32_dpp %0, %0, %1 row_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(a[j]) : "v"(b));
+                if (OP == OP_ADD) asm volatile("v_add_u32 %0, %0, %1" : "+v"(a[j]) : "v"(b));
+                if (OP == OP_MAD_U64_U32) { /* Poly1305's limb product (chacha.hip): 32 x 32 + 64 -> 64, carry-out to an SGPR pair */
+                    uint64_t cy;
+                    asm volatile("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(q[j]), "=s"(cy) : "v"(b), "v"(c));
+                }
             }
         }
     }
