@@ -668,13 +668,13 @@ hipError_t launch_nr(const BsParams &P, const otc_aes_key &K, hipStream_t st)
     uint32_t *tab = nullptr;
     hipError_t e = hipErrorOutOfMemory;
     if (cache) {
-        e = alloc_fault() ? hipErrorOutOfMemory : hipMallocAsync((void **)&tab, (kt_words + ctab_words) * 4, st);
+        e = alloc_fault() ? hipErrorOutOfMemory : ws_alloc((void **)&tab, (kt_words + ctab_words) * 4, st);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             cache = false;
         }
     }
-    if (!cache) e = alloc_fault() ? hipErrorOutOfMemory : hipMallocAsync((void **)&tab, kt_words * 4, st);
+    if (!cache) e = alloc_fault() ? hipErrorOutOfMemory : ws_alloc((void **)&tab, kt_words * 4, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_bs_key_table<MODE == BS_ECB_DEC || is_cbcd<MODE>>, dim3(1), dim3(256), 0, st, K, tab);
     BsParams Q = P;
@@ -694,7 +694,7 @@ hipError_t launch_nr(const BsParams &P, const otc_aes_key &K, hipStream_t st)
          * blocks past the last unit) */
         (void)g;
         if (!P.cl.ctr) {
-            (void)hipFreeAsync(tab, st);
+            (void)ws_free(tab, st);
             return hipErrorInvalidValue;
         }
         hipLaunchKernelGGL((k_aes_bs_claim<NR, MODE>),
@@ -727,7 +727,7 @@ hipError_t launch_nr(const BsParams &P, const otc_aes_key &K, hipStream_t st)
             run(std::false_type{});
     }
     e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(tab, st);
+    const hipError_t f = ws_free(tab, st);
     return e != hipSuccess ? e : f;
 }
 

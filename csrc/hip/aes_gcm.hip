@@ -294,7 +294,7 @@ hipError_t ghash_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws)
     if (!gh_plan(nbytes, pl)) return hipErrorInvalidValue;
     if (pl.nlevels == 0) return hipSuccess;
     if (alloc_fault()) return hipErrorOutOfMemory;
-    return hipMallocAsync(ws, pl.bytes, st);
+    return otc_dev::ws_alloc(ws, pl.bytes, st);
 }
 
 hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], const uint8_t y0[16],
@@ -302,7 +302,7 @@ hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], con
 {
     GhPlan pl;
     if (!gh_plan(nbytes, pl) || (pl.nlevels && !ws)) {
-        if (ws) (void)hipFreeAsync(ws, st);
+        if (ws) (void)otc_dev::ws_free(ws, st);
         return hipErrorInvalidValue;
     }
     GhFinal F{};
@@ -356,7 +356,7 @@ hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], con
         e = hipGetLastError();
     }
     if (ws) {
-        const hipError_t f = hipFreeAsync(ws, st);
+        const hipError_t f = otc_dev::ws_free(ws, st);
         if (e == hipSuccess) e = f;
     }
     return e;

@@ -509,7 +509,7 @@ hipError_t poly1305_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws)
     if (!pl_plan(nbytes, pl)) return hipErrorInvalidValue;
     if (pl.nlevels == 0) return hipSuccess;
     if (alloc_fault()) return hipErrorOutOfMemory;
-    return hipMallocAsync(ws, pl.bytes, st);
+    return otc_dev::ws_alloc(ws, pl.bytes, st);
 }
 
 hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], const uint32_t h0[5],
@@ -518,7 +518,7 @@ hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], 
 {
     PlPlan pl;
     if (!pl_plan(nbytes, pl) || (pl.nlevels && !ws)) {
-        if (ws) (void)hipFreeAsync(ws, st);
+        if (ws) (void)otc_dev::ws_free(ws, st);
         return hipErrorInvalidValue;
     }
     Fe R, Y0;
@@ -574,7 +574,7 @@ hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], 
         e = hipGetLastError();
     }
     if (ws) {
-        const hipError_t f = hipFreeAsync(ws, st);
+        const hipError_t f = otc_dev::ws_free(ws, st);
         if (e == hipSuccess) e = f;
     }
     return e;

@@ -91,6 +91,146 @@ bool alloc_fault()
     return g_fault_alloc.load(std::memory_order_relaxed) >= 0 &&
            g_fault_alloc.fetch_sub(1, std::memory_order_relaxed) == 0;
 }
+
+/* ---- per-call workspaces (otc_device.h ws_alloc / ws_free) ---------------- */
+namespace {
+struct WsBlock {
+    void *p;
+    size_t bytes;
+    int dev;
+    hipEvent_t done;  /* recorded behind the block's last use when it is kept */
+    hipStream_t last; /* the stream it was returned on */
+};
+std::mutex g_ws_mu;
+std::vector<WsBlock> g_ws_kept; /* returned blocks, oldest first */
+std::vector<WsBlock> g_ws_out;  /* handed out: a few at a time, found by a scan */
+/* larger blocks (the CTR tables of calls beyond ~5 GiB) are not kept: their
+ * calls run for milliseconds, and the pool should have the memory back */
+constexpr size_t WS_MAX_BLOCK = (size_t)32 << 20;
+constexpr size_t WS_MAX_KEPT = 16, WS_MAX_KEPT_BYTES = (size_t)64 << 20; /* per device */
+
+bool ws_plain(size_t bytes, hipStream_t st)
+{
+    if (bytes > WS_MAX_BLOCK) return true;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return true; /* unknown: the path that is right under capture */
+    }
+    return cap != hipStreamCaptureStatusNone;
+}
+
+/* the block's last use has run: no stream has to wait for it */
+bool ws_idle(const WsBlock &b)
+{
+    if (hipEventQuery(b.done) == hipSuccess) return true;
+    (void)hipGetLastError(); /* hipErrorNotReady */
+    return false;
+}
+
+bool ws_over(int dev)
+{
+    size_t n = 0, total = 0;
+    for (const WsBlock &b : g_ws_kept)
+        if (b.dev == dev) ++n, total += b.bytes;
+    return n > WS_MAX_KEPT || total > WS_MAX_KEPT_BYTES;
+}
+} // namespace
+
+hipError_t ws_alloc(void **p, size_t bytes, hipStream_t st)
+{
+    *p = nullptr;
+    int dev = 0;
+    const bool plain = ws_plain(bytes, st) || hipGetDevice(&dev) != hipSuccess;
+    if (!plain) {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        /* The smallest kept block that fits without wasting most of itself,
+         * among those that couple no streams: returned on this stream (its
+         * last use is in front of this call anyway), or idle.  A block still
+         * in use on another stream is left alone -- taking it would make
+         * this stream wait for that one's work. */
+        size_t best = g_ws_kept.size();
+        for (size_t i = 0; i < g_ws_kept.size(); ++i) {
+            const WsBlock &b = g_ws_kept[i];
+            if (b.dev == dev && b.bytes >= bytes && (b.bytes <= 4 * bytes || b.bytes <= ((size_t)1 << 20)) &&
+                (best == g_ws_kept.size() || b.bytes < g_ws_kept[best].bytes) && (b.last == st || ws_idle(b)))
+                best = i;
+        }
+        if (best != g_ws_kept.size()) {
+            const WsBlock b = g_ws_kept[best];
+            /* no wait in either case; kept as the safety should a destroyed
+             * stream's handle have come back as `st` */
+            if (hipStreamWaitEvent(st, b.done, 0) == hipSuccess) {
+                g_ws_kept.erase(g_ws_kept.begin() + (long)best);
+                g_ws_out.push_back(b);
+                *p = b.p;
+                return hipSuccess;
+            }
+            (void)hipGetLastError();
+        }
+    }
+    const hipError_t e = hipMallocAsync(p, bytes, st);
+    if (e != hipSuccess || plain) return e;
+    WsBlock b{*p, bytes, dev, nullptr, nullptr};
+    if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        return hipSuccess; /* not tracked: ws_free hands it straight back to the pool */
+    }
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    g_ws_out.push_back(b);
+    return hipSuccess;
+}
+
+hipError_t ws_free(void *p, hipStream_t st)
+{
+    if (!p) return hipSuccess;
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    size_t i = 0;
+    while (i < g_ws_out.size() && g_ws_out[i].p != p) ++i;
+    if (i == g_ws_out.size()) return hipFreeAsync(p, st);
+    WsBlock b = g_ws_out[i];
+    g_ws_out.erase(g_ws_out.begin() + (long)i);
+    if (hipEventRecord(b.done, st) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipEventDestroy(b.done);
+        return hipFreeAsync(p, st);
+    }
+    b.last = st;
+    g_ws_kept.push_back(b);
+    /* Over this device's limits: its oldest idle blocks go back to the pool
+     * (idle: freeing them through `st` waits for nothing).  If the limits
+     * still do not hold -- every other block is in use somewhere -- this
+     * block is not kept either and takes the pool's stream-ordered free. */
+    for (size_t k = 0; k + 1 < g_ws_kept.size() && ws_over(b.dev);) {
+        const WsBlock v = g_ws_kept[k];
+        if (v.dev != b.dev || !ws_idle(v)) {
+            ++k;
+            continue;
+        }
+        g_ws_kept.erase(g_ws_kept.begin() + (long)k);
+        if (hipFreeAsync(v.p, st) != hipSuccess) (void)hipGetLastError();
+        (void)hipEventDestroy(v.done);
+    }
+    if (ws_over(b.dev)) {
+        g_ws_kept.pop_back();
+        (void)hipEventDestroy(b.done);
+        return hipFreeAsync(p, st);
+    }
+    return hipSuccess;
+}
+
+void ws_release_all()
+{
+    std::vector<WsBlock> kept;
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        kept.swap(g_ws_kept);
+    }
+    for (const WsBlock &b : kept) {
+        if (hipEventSynchronize(b.done) != hipSuccess || hipFree(b.p) != hipSuccess) (void)hipGetLastError();
+        (void)hipEventDestroy(b.done);
+    }
+}
 } // namespace otc_dev
 
 extern "C" void otc_fault_inject_alloc(long after) { otc_dev::g_fault_alloc.store(after < 0 ? -1 : after); }
@@ -647,7 +787,7 @@ extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_g
     }
     if (dir == OTC_DIR_ENCRYPT && nbytes) {
         if (int r = ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream)) {
-            if (ws) (void)hipFreeAsync(ws, st);
+            if (ws) (void)otc_dev::ws_free(ws, st);
             return r;
         }
     }
@@ -758,7 +898,7 @@ extern "C" int otc_chacha20_poly1305(const void *in, void *out, size_t nbytes, c
     if (int r = poly1305_ws(nbytes, st, &ws, "chacha20_poly1305")) return r;
     hipError_t e;
     if (dir == OTC_DIR_ENCRYPT && (e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, 1, st)) != hipSuccess) {
-        if (ws) (void)hipFreeAsync(ws, st);
+        if (ws) (void)otc_dev::ws_free(ws, st);
         return hip_fail(e, "chacha20_poly1305 cipher launch");
     }
     /* over the ciphertext: out of an encryption, in of a decryption */

@@ -286,6 +286,29 @@ __device__ __forceinline__ void strace(uint32_t) {}
  * countdown; off (no cost beyond a relaxed load) unless armed. */
 bool alloc_fault();
 
+/* Per-call device workspaces (key and counter tables, hash partials, claim
+ * words), stream-ordered: ws_alloc returns memory that work enqueued on `st`
+ * from now on may use, ws_free takes it back behind everything enqueued on
+ * `st` so far.  Neither waits on the host.  hipMallocAsync / hipFreeAsync by
+ * themselves do not keep that promise: a hipFreeAsync of a block that the
+ * pool had handed out again while its earlier free was still pending waits
+ * for that earlier free -- the second of two calls enqueued back to back
+ * blocked until the first had run (measured, tests/test_gpu_async_contract.py
+ * "ctr32 bitslice across the wrap").  So returned blocks are kept here with
+ * an event recorded behind their last use and the stream they were returned
+ * on.  A call takes a kept block only if it was returned on the call's own
+ * stream (stream order covers it) or its event has fired; otherwise it
+ * allocates afresh.  So no call ever waits, on the host or on the device, for
+ * another stream's work: streams stay as independent as the pool left them.
+ * Per device at most 16 blocks and 64 MiB are kept; beyond that idle blocks
+ * go back to the pool, and a block that cannot be kept takes the pool's own
+ * free.  A capturing stream takes the plain hipMallocAsync / hipFreeAsync
+ * path, which become graph nodes.  ws_release_all (otc_release_resources)
+ * returns the kept blocks. */
+hipError_t ws_alloc(void **p, size_t bytes, hipStream_t st);
+hipError_t ws_free(void *p, hipStream_t st);
+void ws_release_all();
+
 /* Host: CU count of the calling thread's current device, cached per device.
  * Thread-safe (the multi-GPU paths launch from one host thread per GPU): the
  * attribute is immutable, so a relaxed atomic cache is enough. */

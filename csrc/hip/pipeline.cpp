@@ -640,6 +640,7 @@ extern "C" void otc_release_resources(void)
 {
     otc_multi_release();
     otc_rt::aux_release_all();
+    otc_dev::ws_release_all();
 }
 
 /* Logical shards -> devices: shard g runs on device g, or g % ndev when

@@ -238,7 +238,7 @@ int pick_seg_impl(int impl, size_t nbytes, size_t seg_blocks)
 unsigned long long *claim_counter_new(hipStream_t st)
 {
     unsigned long long *ctr = nullptr;
-    if (otc_dev::alloc_fault() || hipMallocAsync((void **)&ctr, 2 * sizeof *ctr, st) != hipSuccess) {
+    if (otc_dev::alloc_fault() || otc_dev::ws_alloc((void **)&ctr, 2 * sizeof *ctr, st) != hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
     }
@@ -368,7 +368,7 @@ hipError_t split_run(const Job &job, bool bs_only, hipStream_t st, int *ran)
     if (hipGetDevice(&dev) != hipSuccess || aux_take(dev, a, cap == hipStreamCaptureStatusNone) != hipSuccess) {
         /* no auxiliary stream: the T-table alone still gives the output */
         (void)hipGetLastError();
-        (void)hipFreeAsync(ctr, st);
+        (void)otc_dev::ws_free(ctr, st);
         return otc_impl::tt_run(job, job.nblocks, st);
     }
     /* first units handed out without a claim (otc_device.h SplitClaim): the
@@ -433,7 +433,7 @@ hipError_t split_run(const Job &job, bool bs_only, hipStream_t st, int *ran)
             (void)hipStreamSynchronize(a.t);
         }
     }
-    const hipError_t f = hipFreeAsync(ctr, st); /* after the join: both kernels are done with it */
+    const hipError_t f = otc_dev::ws_free(ctr, st); /* after the join: both kernels are done with it */
     aux_give(a); /* reusable as soon as the work is enqueued: stream order */
     return e != hipSuccess ? e : f;
 }
@@ -451,7 +451,7 @@ hipError_t claim_alone(uint64_t nunits, uint64_t min_units, hipStream_t st, Laun
     hipError_t e = claim_counter_reset(ctr, false, st);
     if (e == hipSuccess) e = launch(&cl);
     if (e == hipSuccess) e = claim_snapshot(ctr, nunits, cl.pb, false, st);
-    const hipError_t f = hipFreeAsync(ctr, st);
+    const hipError_t f = otc_dev::ws_free(ctr, st);
     return e != hipSuccess ? e : f;
 }
 
