@@ -38,7 +38,7 @@ OBJ    := build/obj
 CPU_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/rc4.c csrc/cpu/aesni.c csrc/cpu/numa.c csrc/cpu/rccl_plan.c csrc/cpu/chacha.c
 CPU_OBJ := $(patsubst csrc/cpu/%.c,$(OBJ)/cpu/%.o,$(CPU_SRC)) $(OBJ)/cpu/bs_selftest.o
 HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/stream_ops.hip
-HIP_OBJ := $(patsubst csrc/hip/%.hip,$(OBJ)/hip/%.o,$(HIP_SRC)) $(OBJ)/hip/engine.o $(OBJ)/hip/split.o $(OBJ)/hip/pipeline.o
+HIP_OBJ := $(patsubst csrc/hip/%.hip,$(OBJ)/hip/%.o,$(HIP_SRC)) $(OBJ)/hip/engine.o $(OBJ)/hip/aead.o $(OBJ)/hip/runtime.o $(OBJ)/hip/split.o $(OBJ)/hip/pipeline.o
 
 BINS := bin/test bin/aes_test bin/aes_ecb_e bin/aes_ecb_d bin/otbench bin/bc_test
 

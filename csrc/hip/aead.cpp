@@ -1,0 +1,398 @@
+/*
+ * aead.cpp -- the hash and authenticated-encryption ops of the C API (otc.h):
+ * GHASH and AES-GCM (counter mode: engine.cpp's ctr32_run; hash: aes_gcm.hip),
+ * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), and batched GCM
+ * (aes_gcm_batch.hip and the batched CTR kernel): the argument checks, what an
+ * op computes on the host (J0, the AAD's hash, the one-time key, the length
+ * blocks) and the order of its launches.
+ */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "aes.h"
+#include "chacha.h"
+#include "otc.h"
+#include "otc_device.h"
+#include "engine_internal.h"
+
+using namespace otc_rt;
+
+/* a hash workspace that could not be had, as the caller's error: no memory,
+ * more bytes than the hash's levels reach (where the op has no check of its
+ * own in front: `too_many`), or whatever else HIP said, behind `what` */
+static int ws_fail(hipError_t e, const char *what, const std::string &nomem, const std::string &too_many = "")
+{
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return set_err(OTC_ERR_NOMEM, nomem);
+    if (e == hipErrorInvalidValue && !too_many.empty()) return set_err(OTC_ERR_ARG, too_many);
+    return hip_fail(e, what);
+}
+
+/* ---- GHASH, the GCM key, AES-GCM ------------------------------------------ */
+extern "C" int otc_ghash_spans(uint64_t *spans, int max) { return otc_impl::ghash_spans(spans, spans ? max : 0); }
+
+extern "C" int otc_ghash(const void *data, size_t nbytes, const uint8_t h[16], const uint8_t y0[16], void *y_dev,
+                         void *stream)
+{
+    Range rg("otc_ghash");
+    if (!h || !y0 || !y_dev) return set_err(OTC_ERR_ARG, "null argument");
+    if ((uintptr_t)y_dev & 3u) return set_err(OTC_ERR_ARG, "ghash: the result must be 4-byte aligned");
+    if (nbytes > ((uint64_t)1 << 36)) return set_err(OTC_ERR_ARG, "ghash: more than 2^36 bytes");
+    if (nbytes && !data) return set_err(OTC_ERR_ARG, "ghash: null buffer");
+    if ((uintptr_t)data & 15u) return set_err(OTC_ERR_ARG, "ghash: device buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    void *ws = nullptr;
+    hipError_t e = otc_impl::ghash_ws_alloc(nbytes, st, &ws);
+    if (e != hipSuccess) return ws_fail(e, "ghash workspace", "ghash: no memory for the tables and partials");
+    e = otc_impl::ghash_run(data, nbytes, h, y0, nullptr, nullptr, y_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, "ghash launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_gcm_key_init(otc_gcm_key *k, const uint8_t *key, int keybits)
+{
+    if (!k || !key) return set_err(OTC_ERR_ARG, "null argument");
+    aes_gcm_context g;
+    if (aes_gcm_setkey(&g, key, (unsigned)keybits)) return set_err(OTC_ERR_ARG, "invalid AES key size (must be 128/192/256)");
+    if (int r = otc_aes_key_init(&k->enc, key, keybits, OTC_DIR_ENCRYPT)) return r;
+    memcpy(k->h, g.h, 16);
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_gcm_key *k, int dir, const uint8_t *iv,
+                           size_t iv_len, const uint8_t *aad, size_t aad_len, void *tag_dev, int impl, void *stream)
+{
+    Range rg("otc_aes_gcm");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (!iv || iv_len == 0) return set_err(OTC_ERR_ARG, "gcm: the IV must have at least 1 byte");
+    if (aad_len && !aad) return set_err(OTC_ERR_ARG, "gcm: null aad");
+    if ((uint64_t)iv_len >> 61 || (uint64_t)aad_len >> 61) return set_err(OTC_ERR_ARG, "gcm: IV or AAD too long");
+    if (!tag_dev || ((uintptr_t)tag_dev & 3u)) return set_err(OTC_ERR_ARG, "gcm: the tag must be 4-byte aligned device memory");
+    if (nbytes > AES_GCM_MAX_BYTES) return set_err(OTC_ERR_ARG, "gcm: a message has at most 2^36 - 32 bytes");
+    if (int r = check_bufs(in, out, nbytes, true, "aes_gcm")) return r;
+    if (int r = check_impl(impl)) return r;
+    hipStream_t st = (hipStream_t)stream;
+
+    /* what does not depend on the data, on the host */
+    aes_gcm_context g;
+    aes_import_rk32(&g.enc, k->enc.rk, k->enc.nr);
+    aes_gcm_set_h(&g, k->h);
+    uint8_t j0[16], ekj0[16], ctr[16], y0[16] = {0}, lenblock[16];
+    aes_gcm_j0(&g, iv, iv_len, j0);
+    aes_crypt_ecb(&g.enc, AES_ENCRYPT, j0, ekj0);
+    memcpy(ctr, j0, 16);
+    for (int i = 15; i >= 12; --i)
+        if (++ctr[i]) break;
+    aes_ghash(&g, y0, aad, aad_len);
+    store_be64(lenblock, (uint64_t)aad_len * 8);
+    store_be64(lenblock + 8, (uint64_t)nbytes * 8);
+
+    /* the hash's memory first: a failure leaves out and the tag untouched */
+    void *ws = nullptr;
+    hipError_t e = otc_impl::ghash_ws_alloc(nbytes, st, &ws);
+    if (e != hipSuccess) return ws_fail(e, "gcm workspace", "gcm: no memory for the hash's tables and partials");
+    if (dir == OTC_DIR_ENCRYPT && nbytes) {
+        if (int r = ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream)) {
+            if (ws) (void)otc_dev::ws_free(ws, st);
+            return r;
+        }
+    }
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    e = otc_impl::ghash_run(dir == OTC_DIR_ENCRYPT ? out : in, nbytes, k->h, y0, lenblock, ekj0, tag_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm hash launch");
+    if (dir == OTC_DIR_DECRYPT && nbytes) return ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream);
+    return OTC_OK;
+}
+
+/* ---- ChaCha20, Poly1305, ChaCha20-Poly1305 (RFC 8439) ---------------------- */
+/* what every ChaCha20 call checks before anything is launched: the buffers
+ * (any alignment; the same buffer or disjoint) and the 32-bit block counter,
+ * which this engine never lets wrap */
+static int chacha_check(const void *in, const void *out, size_t nbytes, uint32_t counter, const char *what)
+{
+    const uint64_t nblk = (uint64_t)nbytes / 64 + (nbytes % 64 ? 1 : 0);
+    if ((uint64_t)counter + nblk > ((uint64_t)1 << 32))
+        return set_err(OTC_ERR_ARG, std::string(what) + ": the 32-bit block counter would pass 2^32 - 1");
+    if (nbytes == 0) return OTC_OK;
+    if (!in || !out) return set_err(OTC_ERR_ARG, std::string(what) + ": null buffer");
+    if (partial_overlap(in, out, nbytes))
+        return set_err(OTC_ERR_ARG, std::string(what) + ": input and output overlap partially");
+    return OTC_OK;
+}
+
+extern "C" int otc_chacha20(const void *in, void *out, size_t nbytes, const uint8_t key[32], const uint8_t nonce[12],
+                            uint32_t counter, void *stream)
+{
+    Range rg("otc_chacha20");
+    if (!key || !nonce) return set_err(OTC_ERR_ARG, "chacha20: null key or nonce");
+    if (int r = chacha_check(in, out, nbytes, counter, "chacha20")) return r;
+    const hipError_t e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, counter, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "chacha20 launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_poly1305_spans(uint64_t *spans, int max) { return otc_impl::poly1305_spans(spans, spans ? max : 0); }
+
+/* the hash over device data from a host-side state: workspace first, then the kernels */
+static int poly1305_dev(const void *data, size_t nbytes, const poly1305_state &ps, const uint8_t *lenblock, bool pad16,
+                        void *tag_dev, void *ws, hipStream_t st, const char *what)
+{
+    const hipError_t e = otc_impl::poly1305_run(data, nbytes, ps.r, ps.h, ps.s, lenblock, pad16, tag_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return OTC_OK;
+}
+
+static int poly1305_ws(size_t nbytes, hipStream_t st, void **ws, const char *what)
+{
+    const hipError_t e = otc_impl::poly1305_ws_alloc(nbytes, st, ws);
+    if (e == hipSuccess) return OTC_OK;
+    return ws_fail(e, what, std::string(what) + ": no memory for the hash's partials", std::string(what) + ": too many bytes");
+}
+
+extern "C" int otc_poly1305(const void *data, size_t nbytes, const uint8_t key[32], void *tag_dev, void *stream)
+{
+    Range rg("otc_poly1305");
+    if (!key || !tag_dev) return set_err(OTC_ERR_ARG, "poly1305: null argument");
+    if ((uintptr_t)tag_dev & 3u) return set_err(OTC_ERR_ARG, "poly1305: the tag must be 4-byte aligned");
+    if (nbytes && !data) return set_err(OTC_ERR_ARG, "poly1305: null buffer");
+    if (nbytes && ((uintptr_t)data & 15u)) return set_err(OTC_ERR_ARG, "poly1305: device buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    poly1305_state ps;
+    poly1305_init(&ps, key);
+    void *ws = nullptr;
+    if (int r = poly1305_ws(nbytes, st, &ws, "poly1305")) return r;
+    return poly1305_dev(data, nbytes, ps, nullptr, false, tag_dev, ws, st, "poly1305 launch");
+}
+
+extern "C" int otc_chacha20_poly1305(const void *in, void *out, size_t nbytes, const uint8_t key[32], int dir,
+                                     const uint8_t nonce[12], const uint8_t *aad, size_t aad_len, void *tag_dev,
+                                     void *stream)
+{
+    Range rg("otc_chacha20_poly1305");
+    if (!key || !nonce) return set_err(OTC_ERR_ARG, "chacha20_poly1305: null key or nonce");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (aad_len && !aad) return set_err(OTC_ERR_ARG, "chacha20_poly1305: null aad");
+    if (!tag_dev || ((uintptr_t)tag_dev & 3u))
+        return set_err(OTC_ERR_ARG, "chacha20_poly1305: the tag must be 4-byte aligned device memory");
+    if ((uint64_t)nbytes > CHACHA20_POLY1305_MAX_BYTES)
+        return set_err(OTC_ERR_ARG, "chacha20_poly1305: a message has at most (2^32 - 1) * 64 bytes");
+    if (int r = check_bufs(in, out, nbytes, true, "chacha20_poly1305")) return r;
+    hipStream_t st = (hipStream_t)stream;
+
+    /* what does not depend on the data, on the host: the one-time key (block
+     * 0), the hash state after the AAD, the length block */
+    uint8_t b0[64], lenblock[16];
+    chacha20_block(key, nonce, 0, b0);
+    poly1305_state ps;
+    poly1305_init(&ps, b0);
+    poly1305_pad16(&ps, aad, aad_len);
+    for (int i = 0; i < 8; ++i) {
+        lenblock[i] = (uint8_t)((uint64_t)aad_len >> (8 * i));
+        lenblock[8 + i] = (uint8_t)((uint64_t)nbytes >> (8 * i));
+    }
+
+    /* the hash's memory first: a failure leaves out and the tag untouched */
+    void *ws = nullptr;
+    if (int r = poly1305_ws(nbytes, st, &ws, "chacha20_poly1305")) return r;
+    hipError_t e;
+    if (dir == OTC_DIR_ENCRYPT && (e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, 1, st)) != hipSuccess) {
+        if (ws) (void)otc_dev::ws_free(ws, st);
+        return hip_fail(e, "chacha20_poly1305 cipher launch");
+    }
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    if (int r = poly1305_dev(dir == OTC_DIR_ENCRYPT ? out : in, nbytes, ps, lenblock, true, tag_dev, ws, st,
+                             "chacha20_poly1305 hash launch"))
+        return r;
+    if (dir == OTC_DIR_DECRYPT && (e = otc_impl::chacha20_run(in, out, nbytes, key, nonce, 1, st)) != hipSuccess)
+        return hip_fail(e, "chacha20_poly1305 cipher launch");
+    return OTC_OK;
+}
+
+/* ---- batched GCM: many records, own IVs, one tag array --------------------- */
+extern "C" int otc_gcm_batch_spans(uint64_t *spans, int max) { return otc_impl::gcm_batch_spans(spans, spans ? max : 0); }
+
+extern "C" size_t otc_gcm_batch_table_bytes(void) { return otc_impl::gcm_batch_table_bytes(); }
+
+extern "C" size_t otc_gcm_batch_ws_bytes(size_t nmsg) { return nmsg * 32; /* J0[], then E_K(J0)[] */ }
+
+extern "C" int otc_gcm_batch_tables(const otc_gcm_key *k, void *tab_dev, void *stream)
+{
+    Range rg("otc_gcm_batch_tables");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (!tab_dev || ((uintptr_t)tab_dev & 15u))
+        return set_err(OTC_ERR_ARG, "gcm_batch: the tables must be 16-byte aligned device memory");
+    const hipError_t e = otc_impl::gcm_batch_tables(k->h, tab_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gcm_batch tables launch");
+    return OTC_OK;
+}
+
+extern "C" int64_t otc_gcm_batch_plan(const otc_gcm_msg *msgs, size_t nmsg, int tile_blocks, otc_ctr_msg *ctr_msgs,
+                                      uint32_t *tile_msg, uint64_t *tile_first)
+{
+    if (!check_tile_blocks(tile_blocks))
+        return set_err(OTC_ERR_ARG, "gcm_batch: tile_blocks must be 64, 128 or 256");
+    if (nmsg == 0) return 0;
+    if (!msgs) return set_err(OTC_ERR_ARG, "gcm_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "gcm_batch: record " + std::to_string(m) + ": " + what);
+    };
+    struct Iv {
+        uint64_t lo, hi;
+        size_t m;
+    };
+    std::vector<Iv> outs; /* the non-empty outputs, to find records that overlap */
+    for (size_t m = 0; m < nmsg; ++m) {
+        const otc_gcm_msg &d = msgs[m];
+        /* at most 65536 blocks: the counter's low 32 bits, started at 2, never wrap */
+        if (d.nbytes > OTC_GCM_BATCH_MAX_BYTES) return bad(m, "more than 1 MiB of data (use otc_aes_gcm)");
+        if (d.aad_bytes > OTC_GCM_BATCH_MAX_AAD) return bad(m, "more than 64 KiB of AAD");
+        if (d.aad_bytes && !d.aad) return bad(m, "null aad");
+        if (!d.nbytes) continue;
+        if (!d.in || !d.out) return bad(m, "null buffer");
+        if ((d.in | d.out) & 15u) return bad(m, "data buffers must be 16-byte aligned");
+        if (partial_overlap((const void *)d.in, (const void *)d.out, d.nbytes))
+            return bad(m, "input and output overlap partially");
+        outs.push_back({d.out, d.out + d.nbytes, m});
+    }
+    std::sort(outs.begin(), outs.end(), [](const Iv &a, const Iv &b) { return a.lo < b.lo; });
+    for (size_t i = 1; i < outs.size(); ++i)
+        if (outs[i].lo < outs[i - 1].hi) return bad(outs[i].m, "its output overlaps another record's");
+    for (size_t m = 0; m < nmsg; ++m) { /* no record reads what another writes */
+        const otc_gcm_msg &d = msgs[m];
+        if (!d.nbytes) continue;
+        auto it = std::upper_bound(outs.begin(), outs.end(), d.in,
+                                   [](uint64_t a, const Iv &o) { return a < o.hi; }); /* first output ending past in */
+        for (; it != outs.end() && it->lo < d.in + d.nbytes; ++it)
+            if (it->m != m) return bad(m, "its input overlaps another record's output");
+    }
+    for (size_t m = 0; m < nmsg; ++m) { /* an encryption writes every output before the hash reads the AADs */
+        const otc_gcm_msg &d = msgs[m];
+        if (!d.aad_bytes) continue;
+        auto it = std::upper_bound(outs.begin(), outs.end(), d.aad, [](uint64_t a, const Iv &o) { return a < o.hi; });
+        if (it != outs.end() && it->lo < d.aad + d.aad_bytes) return bad(m, "its AAD overlaps a record's output");
+    }
+    const uint64_t tile_bytes = 16ull * (uint64_t)tile_blocks;
+    uint64_t t = 0;
+    for (size_t m = 0; m < nmsg; ++m) {
+        const uint64_t nt = (msgs[m].nbytes + tile_bytes - 1) / tile_bytes;
+        if (ctr_msgs) ctr_msgs[m] = otc_ctr_msg{msgs[m].in, msgs[m].out, msgs[m].nbytes, 0, 0, 0, 0};
+        t = tile_map_fill(tile_msg, tile_first, m, t, nt);
+    }
+    return (int64_t)t;
+}
+
+/* 16 lanes per record for short records, 64 for long ones: measured on
+ * uniform batches, 16 wins at 1, 4 and 8 KiB records (x3.4, x1.8, x1.2), 64 at
+ * 16 KiB (x1.3); a mean of 768 hashed blocks (12 KiB), between the last two,
+ * is where the choice changes -- nothing between them was measured.  SUPPOSED,
+ * not measured: a group of records waits for the serial chain of its longest,
+ * nb / lanes multiplications, so one record above 4096 blocks also takes 64;
+ * no batch of mixed sizes has been timed (aes_gcm_batch.hip, docs/PERF.md
+ * "Batched AES-GCM"). */
+extern "C" int otc_gcm_batch_lanes(const otc_gcm_msg *msgs, size_t nmsg)
+{
+    uint64_t total = 0;
+    for (size_t m = 0; msgs && m < nmsg; ++m) {
+        const uint64_t nb = (msgs[m].aad_bytes + 15) / 16 + (msgs[m].nbytes + 15) / 16 + 1;
+        if (nb > 4096) return otc_impl::GB_LANES_LONG;
+        total += nb;
+    }
+    return nmsg && total / nmsg > 768 ? otc_impl::GB_LANES_LONG : otc_impl::GB_LANES_SHORT;
+}
+
+/* what otc_ghash_batch and otc_aes_gcm_batch check alike */
+static int gcm_batch_common(const otc_gcm_msg *msgs_dev, const void *tab_dev, const void *out16, const char *out_name,
+                            int &lanes)
+{
+    if (lanes == 0) lanes = otc_impl::GB_LANES_LONG;
+    if (lanes != otc_impl::GB_LANES_SHORT && lanes != otc_impl::GB_LANES_LONG)
+        return set_err(OTC_ERR_ARG, "gcm_batch: lanes must be 16 or 64 (0: 64)");
+    if (!msgs_dev || !tab_dev || !out16) return set_err(OTC_ERR_ARG, "gcm_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "gcm_batch: misaligned descriptor array");
+    if ((uintptr_t)tab_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_batch: the tables must be 16-byte aligned");
+    if ((uintptr_t)out16 & 15u) return set_err(OTC_ERR_ARG, std::string("gcm_batch: ") + out_name + " must be 16-byte aligned");
+    return OTC_OK;
+}
+
+extern "C" int otc_ghash_batch(const otc_gcm_msg *msgs_dev, size_t nmsg, const void *tab_dev, void *s_dev, int lanes,
+                               void *stream)
+{
+    Range rg("otc_ghash_batch");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = gcm_batch_common(msgs_dev, tab_dev, s_dev, "the hash array", lanes)) return r;
+    const hipError_t e = otc_impl::ghash_batch_run(msgs_dev, nmsg, tab_dev, s_dev, nullptr, nullptr, 16, nullptr, false,
+                                                   lanes, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "ghash_batch launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_gcm_batch(const otc_gcm_msg *msgs_dev, otc_ctr_msg *ctr_msgs_dev, const uint32_t *tile_msg_dev,
+                                 const uint64_t *tile_first_dev, uint64_t ntiles, int tile_blocks, size_t nmsg,
+                                 const otc_gcm_key *k, const otc_aes_key *key_dev, const void *tab_dev, int dir,
+                                 const uint8_t *ivs_dev, void *tags_dev, const uint8_t *expect_dev, int tag_bytes,
+                                 uint8_t *ok_dev, void *ws_dev, int lanes, void *stream)
+{
+    Range rg("otc_aes_gcm_batch");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (!check_tile_blocks(tile_blocks))
+        return set_err(OTC_ERR_ARG, "gcm_batch: tile_blocks must be 64, 128 or 256");
+    if (tag_bytes < 4 || tag_bytes > 16) return set_err(OTC_ERR_ARG, "gcm_batch: a tag has 4 to 16 bytes");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = gcm_batch_common(msgs_dev, tab_dev, tags_dev, "the tag array", lanes)) return r;
+    if (!ctr_msgs_dev || !key_dev || !ws_dev) return set_err(OTC_ERR_ARG, "gcm_batch: null array");
+    if (ntiles && (!tile_msg_dev || !tile_first_dev)) return set_err(OTC_ERR_ARG, "gcm_batch: null tile map");
+    if ((((uintptr_t)ctr_msgs_dev) | ((uintptr_t)key_dev) | ((uintptr_t)tile_first_dev)) & 7u ||
+        ((uintptr_t)tile_msg_dev & 3u))
+        return set_err(OTC_ERR_ARG, "gcm_batch: misaligned descriptor arrays");
+    if ((uintptr_t)ws_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_batch: the workspace must be 16-byte aligned");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "gcm_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * (size_t)tag_bytes;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * 16 && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "gcm_batch: the expected tags overlap the computed tags or the verdicts");
+    }
+    if (!ivs_dev) return set_err(OTC_ERR_ARG, "gcm_batch: null IVs");
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+    uint8_t *j0 = (uint8_t *)ws_dev, *ekj0 = j0 + nmsg * 16;
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+
+    hipError_t e = otc_impl::gcm_batch_prep(ivs_dev, nmsg, ctr_msgs_dev, j0, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_batch prep launch");
+    /* E_K(J0[]): the grid T-table kernel, ECB over nmsg blocks */
+    const otc_impl::Job job{otc_impl::JOB_ECB_ENC, j0, ekj0, nmsg, &k->enc, nullptr, 0};
+    if ((e = otc_impl::tt_run(job, nmsg, st)) != hipSuccess) return hip_fail(e, "gcm_batch E_K(J0) launch");
+    /* the CTR half: the batched kernel's static split (the claimed form
+     * allocates its counter) */
+    auto ctr = [&] {
+        return ntiles ? otc_impl::tt_ctr_batch(ctr_msgs_dev, key_dev, tile_msg_dev, tile_first_dev, ntiles, tile_blocks,
+                                               k->enc.nr, st, nullptr)
+                      : hipSuccess;
+    };
+    if (enc && (e = ctr()) != hipSuccess) return hip_fail(e, "gcm_batch ctr launch");
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    e = otc_impl::ghash_batch_run(msgs_dev, nmsg, tab_dev, tags_dev, ekj0, enc ? nullptr : expect_dev, tag_bytes,
+                                  enc ? nullptr : ok_dev, enc, lanes, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_batch hash launch");
+    if (!enc) {
+        if ((e = ctr()) != hipSuccess) return hip_fail(e, "gcm_batch ctr launch");
+        if ((e = otc_impl::gcm_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+            return hip_fail(e, "gcm_batch wipe launch");
+    }
+    return OTC_OK;
+}
+

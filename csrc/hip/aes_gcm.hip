@@ -38,24 +38,21 @@
  * H^64, H^2048, ... by repeated squaring -- are computed on the host, which
  * knows H, and travel by value.
  *
- * Bit order: the leftmost bit of a block (bit 7 of byte 0) is x^0, "times x"
- * is a right shift of the byte string, reduction by 0xE1 || 0^120 -- the same
- * convention as csrc/cpu/aes.c, whose nibble tables are this file's byte
- * tables in small.  Blocks and table entries stay in memory byte order
- * (little-endian words); only the doubling works on big-endian words.
+ * The multiplication, the doubling, the table builder and the bit order they
+ * keep are in ghash_dev.h, shared with aes_gcm_batch.hip; the end-aligned
+ * levels and their workspace in otc_device.h, shared with chacha.hip.
  */
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstring>
 
 #include "aes.h"
+#include "ghash_dev.h"
 #include "otc_device.h"
 #include "otc_kernels.h"
 
 namespace otc_impl {
 
-using otc_dev::alloc_fault;
 using otc_dev::ld_u4;
 
 namespace {
@@ -64,55 +61,11 @@ constexpr uint32_t GH_RUN = 32;                 /* blocks per lane in a wave spa
 constexpr uint32_t GH_BATCH = 8;                /* passes loaded ahead */
 constexpr uint32_t GH_SPAN = 64 * GH_RUN;       /* blocks of a wave span */
 constexpr uint32_t GH_WAVES = 16;               /* wave spans of a workgroup */
-constexpr uint32_t GH_TAB = 16 * 256;           /* entries of one constant's table */
 constexpr uint32_t GH_ACC_STRIDE = 65;          /* accumulators of a wave, padded off one bank */
-constexpr uint32_t GH_LDS = (2 * GH_TAB + GH_WAVES * GH_ACC_STRIDE) * 16;
+constexpr uint32_t GH_LDS = (2 * GF_TAB + GH_WAVES * GH_ACC_STRIDE) * 16;
 constexpr int GH_MAX_LEVELS = 3;
 static_assert(GH_RUN % GH_BATCH == 0, "a wave span is whole batches");
 static_assert(GH_LDS <= 160 * 1024, "two tables and the accumulators must fit the CU's LDS");
-
-__device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
-
-/* x . C by the positional table of C (LDS): 16 reads of 16 B */
-__device__ __forceinline__ uint4 gh_mul(const uint4 *T, uint4 x)
-{
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-    uint4 r = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int p = 0; p < 16; ++p) r = xor4(r, T[p * 256 + ((w[p >> 2] >> (8 * (p & 3))) & 0xFFu)]);
-    return r;
-}
-
-/* big-endian words <-> memory-order words */
-__device__ __forceinline__ uint4 gh_swap(uint4 v)
-{
-    return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
-}
-/* v . x on big-endian words */
-__device__ __forceinline__ uint4 gh_mulx(uint4 v)
-{
-    const uint32_t carry = v.w & 1u;
-    return make_uint4((v.x >> 1) ^ (carry ? 0xE1000000u : 0u), (v.y >> 1) | (v.x << 31), (v.z >> 1) | (v.y << 31),
-                      (v.w >> 1) | (v.z << 31));
-}
-
-struct GhConsts {
-    uint4 c[2 * GH_MAX_LEVELS]; /* per level: C^64, then C; memory order */
-};
-
-/* one workgroup per (table, byte position), one thread per byte value */
-__global__ __launch_bounds__(256) void k_ghash_tables(GhConsts K, uint4 *tab)
-{
-    const uint32_t t = blockIdx.x >> 4, pos = blockIdx.x & 15u, b = threadIdx.x;
-    uint4 v = gh_swap(K.c[t]);
-    for (uint32_t i = 0; i < 8 * pos; ++i) v = gh_mulx(v);
-    uint4 e = make_uint4(0, 0, 0, 0);
-    for (uint32_t k = 0; k < 8; ++k) { /* the byte's leftmost bit is the lowest power */
-        if (b & (0x80u >> k)) e = xor4(e, v);
-        v = gh_mulx(v);
-    }
-    tab[(size_t)t * GH_TAB + pos * 256 + b] = gh_swap(e);
-}
 
 struct GhLevel {
     const uint8_t *in;  /* nblocks blocks, 16-byte aligned; the last one may be short */
@@ -120,7 +73,7 @@ struct GhLevel {
     uint64_t nblocks;   /* ceil(nbytes / 16), >= 1 */
     uint64_t nspans;    /* ceil(nblocks / GH_SPAN) */
     uint64_t pad;       /* nspans * GH_SPAN - nblocks zero blocks in front */
-    const uint4 *tab;   /* [2][GH_TAB]: this level's C^64, then C */
+    const uint4 *tab;   /* [2][GF_TAB]: this level's C^64, then C */
     uint4 *out;         /* nspans partials */
     uint4 y0;           /* XORed into block 0 */
 };
@@ -145,9 +98,9 @@ template <bool NT>
 __global__ __launch_bounds__(64 * GH_WAVES) void k_ghash_level(GhLevel P)
 {
     extern __shared__ __attribute__((aligned(16))) uint4 gh_lds[];
-    uint4 *const T64 = gh_lds, *const T1 = gh_lds + GH_TAB, *const acc = gh_lds + 2 * GH_TAB;
+    uint4 *const T64 = gh_lds, *const T1 = gh_lds + GF_TAB, *const acc = gh_lds + 2 * GF_TAB;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    for (uint32_t i = tid; i < 2 * GH_TAB; i += 64 * GH_WAVES) gh_lds[i] = ld_u4<false, true>(P.tab + i);
+    for (uint32_t i = tid; i < 2 * GF_TAB; i += 64 * GH_WAVES) gh_lds[i] = ld_u4<false, true>(P.tab + i);
     __syncthreads();
     const uint64_t ngroups = (P.nspans + GH_WAVES - 1) / GH_WAVES;
     for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
@@ -217,46 +170,13 @@ uint4 u4_of(const uint8_t b[16])
     return v;
 }
 
-/* blocks and spans of every level over nbytes of data */
-struct GhPlan {
-    int nlevels;
-    uint64_t nblocks[GH_MAX_LEVELS], nspans[GH_MAX_LEVELS];
-    size_t bytes; /* tables, then every level's partials */
-};
-bool gh_plan(uint64_t nbytes, GhPlan &pl)
-{
-    pl.nlevels = 0;
-    pl.bytes = 0;
-    if (nbytes > UINT64_MAX - 15) return false;
-    uint64_t n = (nbytes + 15) / 16;
-    while (n) {
-        if (pl.nlevels == GH_MAX_LEVELS) return false;
-        const uint64_t sp = (n + GH_SPAN - 1) / GH_SPAN;
-        pl.nblocks[pl.nlevels] = n;
-        pl.nspans[pl.nlevels] = sp;
-        pl.bytes += (size_t)sp * 16;
-        ++pl.nlevels;
-        n = sp > 1 ? sp : 0;
-    }
-    pl.bytes += (size_t)pl.nlevels * 2 * GH_TAB * 16;
-    return true;
-}
+/* the workspace: every level's two tables, then every level's partials */
+constexpr otc_dev::HashShape GH_SHAPE{GH_SPAN, GH_BATCH, GH_WAVES, GH_MAX_LEVELS, 16, 2 * GF_TAB * 16};
 
 hipError_t gh_launch_level(bool nt, const GhLevel &P, hipStream_t st)
 {
-    static std::atomic<uint64_t> opted{0}; /* the opt-in above 64 KiB of dynamic LDS, once per device */
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = otc_dev::lds_opt_in<k_ghash_level<true>, k_ghash_level<false>>(GH_LDS);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(opted.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute((const void *)k_ghash_level<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GH_LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)k_ghash_level<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)GH_LDS);
-        if (e != hipSuccess) return e;
-        opted.fetch_or(bit, std::memory_order_acq_rel);
-    }
     const uint64_t ngroups = (P.nspans + GH_WAVES - 1) / GH_WAVES, cus = (uint64_t)otc_dev::device_cus();
     const dim3 g((unsigned)(ngroups < cus ? ngroups : cus)), b(64 * GH_WAVES);
     if (nt)
@@ -268,40 +188,21 @@ hipError_t gh_launch_level(bool nt, const GhLevel &P, hipStream_t st)
 
 } // namespace
 
-int ghash_spans(uint64_t *spans, int max)
-{
-    const uint64_t all[] = {64 * 16ull,                            /* a pass */
-                            GH_BATCH * 64 * 16ull,                 /* a batch of passes */
-                            GH_SPAN * 16ull,                       /* a wave span */
-                            (uint64_t)GH_WAVES * GH_SPAN * 16,     /* a workgroup's spans */
-                            (uint64_t)GH_SPAN * GH_SPAN * 16,      /* a level-2 span */
-                            (uint64_t)GH_SPAN * GH_SPAN * GH_SPAN * 16};
-    const int n = (int)(sizeof all / sizeof all[0]);
-    for (int i = 0; i < n && i < max; ++i) spans[i] = all[i];
-    return n;
-}
+int ghash_spans(uint64_t *spans, int max) { return otc_dev::hash_spans(GH_SHAPE, spans, max); }
 
 bool ghash_fits(uint64_t nbytes)
 {
-    GhPlan pl;
-    return gh_plan(nbytes, pl);
+    otc_dev::HashLevels pl;
+    return otc_dev::hash_levels(GH_SHAPE, nbytes, pl);
 }
 
-hipError_t ghash_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws)
-{
-    *ws = nullptr;
-    GhPlan pl;
-    if (!gh_plan(nbytes, pl)) return hipErrorInvalidValue;
-    if (pl.nlevels == 0) return hipSuccess;
-    if (alloc_fault()) return hipErrorOutOfMemory;
-    return otc_dev::ws_alloc(ws, pl.bytes, st);
-}
+hipError_t ghash_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws) { return otc_dev::hash_ws_alloc(GH_SHAPE, nbytes, st, ws); }
 
 hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], const uint8_t y0[16],
                      const uint8_t *lenblock, const uint8_t *ekj0, void *out16, void *ws, hipStream_t st)
 {
-    GhPlan pl;
-    if (!gh_plan(nbytes, pl) || (pl.nlevels && !ws)) {
+    otc_dev::HashLevels pl;
+    if (!otc_dev::hash_levels(GH_SHAPE, nbytes, pl) || (pl.nlevels && !ws)) {
         if (ws) (void)otc_dev::ws_free(ws, st);
         return hipErrorInvalidValue;
     }
@@ -318,7 +219,7 @@ hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], con
     hipError_t e = hipSuccess;
     if (pl.nlevels) {
         /* level l multiplies by C_l = H^(GH_SPAN^l) and, across lanes, C_l^64 */
-        GhConsts K{};
+        GfConsts<2 * GH_MAX_LEVELS> K{}; /* per level: C^64, then C */
         uint8_t c[16], c64[16];
         memcpy(c, h, 16);
         for (int l = 0; l < pl.nlevels; ++l) {
@@ -329,8 +230,8 @@ hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], con
             memcpy(c, c64, 16); /* C^64, squared on to C^GH_SPAN */
             for (uint32_t p = 64; p < GH_SPAN; p *= 2) aes_gf128_mul(c, c, c);
         }
-        uint4 *tab = (uint4 *)ws, *part = tab + (size_t)pl.nlevels * 2 * GH_TAB;
-        hipLaunchKernelGGL(k_ghash_tables, dim3((unsigned)pl.nlevels * 2 * 16), dim3(256), 0, st, K, tab);
+        uint4 *tab = (uint4 *)ws, *part = tab + (size_t)pl.nlevels * 2 * GF_TAB;
+        hipLaunchKernelGGL(k_gf128_tables<2 * GH_MAX_LEVELS>, dim3((unsigned)pl.nlevels * 2 * 16), dim3(256), 0, st, K, tab);
         e = hipGetLastError();
         const uint8_t *in = (const uint8_t *)data;
         uint64_t in_bytes = nbytes;
@@ -341,7 +242,7 @@ hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], con
             P.nblocks = pl.nblocks[l];
             P.nspans = pl.nspans[l];
             P.pad = P.nspans * GH_SPAN - P.nblocks;
-            P.tab = tab + (size_t)l * 2 * GH_TAB;
+            P.tab = tab + (size_t)l * 2 * GF_TAB;
             P.out = part;
             P.y0 = l == 0 ? u4_of(y0) : make_uint4(0, 0, 0, 0);
             e = gh_launch_level(l == 0, P, st); /* the data streams once; partials are read back from L2 */

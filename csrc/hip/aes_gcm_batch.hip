@@ -45,10 +45,8 @@
  * The tables of H^16, H^64 and H (16 x 256 entries of 16 B per constant, see
  * aes_gcm.hip) come from a per-KEY image in device memory that
  * gcm_batch_tables builds once when a batch is planned; a workgroup copies
- * H^L and H to LDS.  gh_mul / gh_swap / gh_mulx and the table builder are
- * COPIES of aes_gcm.hip's: moving them to a shared header would have to leave
- * aes_gcm.o's instructions unchanged, and these few lines are not worth that
- * risk.
+ * H^L and H to LDS.  gh_mul / gh_swap / gh_mulx, the table builder and the
+ * bit order they keep are ghash_dev.h's, shared with aes_gcm.hip.
  *
  * Nothing here reads at or past the end of a record's data or AAD: whole
  * 16-byte loads only where 16 bytes are inside, bytes otherwise.  Every value
@@ -56,10 +54,10 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstring>
 
 #include "aes.h"
+#include "ghash_dev.h"
 #include "otc_device.h"
 #include "otc_kernels.h"
 
@@ -71,56 +69,12 @@ namespace {
 
 constexpr uint32_t GB_BATCH = 4;                 /* passes loaded ahead */
 constexpr uint32_t GB_WAVES = 16;                /* waves of a workgroup */
-constexpr uint32_t GB_TAB = 16 * 256;            /* entries of one constant's table */
 constexpr uint32_t GB_NTAB = 3;                  /* the per-key image: H^16, H^64, H */
 constexpr uint32_t GB_ACC = GB_WAVES * 68;       /* accumulators: 64 records x 17 or 16 records x 65 */
-constexpr uint32_t GB_LDS = (2 * GB_TAB + GB_ACC) * 16 + 64 * 4;
+constexpr uint32_t GB_LDS = (2 * GF_TAB + GB_ACC) * 16 + 64 * 4;
 static_assert(GB_LDS <= 160 * 1024, "two tables, the accumulators and the fold starts must fit the CU's LDS");
 
 typedef const __attribute__((address_space(1))) uint8_t *gptr8;
-
-__device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
-
-/* x . C by the positional table of C (LDS): 16 reads of 16 B */
-__device__ __forceinline__ uint4 gh_mul(const uint4 *T, uint4 x)
-{
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-    uint4 r = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int p = 0; p < 16; ++p) r = xor4(r, T[p * 256 + ((w[p >> 2] >> (8 * (p & 3))) & 0xFFu)]);
-    return r;
-}
-
-/* big-endian words <-> memory-order words */
-__device__ __forceinline__ uint4 gh_swap(uint4 v)
-{
-    return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
-}
-/* v . x on big-endian words */
-__device__ __forceinline__ uint4 gh_mulx(uint4 v)
-{
-    const uint32_t carry = v.w & 1u;
-    return make_uint4((v.x >> 1) ^ (carry ? 0xE1000000u : 0u), (v.y >> 1) | (v.x << 31), (v.z >> 1) | (v.y << 31),
-                      (v.w >> 1) | (v.z << 31));
-}
-
-struct GbConsts {
-    uint4 c[GB_NTAB]; /* H^16, H^64, H; memory order */
-};
-
-/* one workgroup per (table, byte position), one thread per byte value */
-__global__ __launch_bounds__(256) void k_gcm_batch_tables(GbConsts K, uint4 *tab)
-{
-    const uint32_t t = blockIdx.x >> 4, pos = blockIdx.x & 15u, b = threadIdx.x;
-    uint4 v = gh_swap(K.c[t]);
-    for (uint32_t i = 0; i < 8 * pos; ++i) v = gh_mulx(v);
-    uint4 e = make_uint4(0, 0, 0, 0);
-    for (uint32_t k = 0; k < 8; ++k) { /* the byte's leftmost bit is the lowest power */
-        if (b & (0x80u >> k)) e = xor4(e, v);
-        v = gh_mulx(v);
-    }
-    tab[(size_t)t * GB_TAB + pos * 256 + b] = gh_swap(e);
-}
 
 /* one record as the hash sees it */
 struct GbRec {
@@ -158,7 +112,7 @@ __device__ __forceinline__ uint4 gb_block(const GbRec &R, uint64_t i)
 struct GbParams {
     const otc_gcm_msg *msgs;
     uint64_t nmsg;
-    const uint4 *tab;      /* [3][GB_TAB]: H^16, H^64, H */
+    const uint4 *tab;      /* [3][GF_TAB]: H^16, H^64, H */
     uint4 *out;            /* nmsg x 16: GHASH, or with ekj0 the tag (zero where ok[m] becomes 0) */
     const uint4 *ekj0;     /* nmsg x 16 or null */
     const uint8_t *expect; /* nmsg x tag_bytes or null (with ok) */
@@ -187,12 +141,12 @@ __global__ __launch_bounds__(64 * GB_WAVES) void k_ghash_batch(GbParams P)
     constexpr uint32_t STRIDE = L + 1;             /* accumulators of a record, padded off one bank */
     static_assert(NREC <= 64 && NREC * STRIDE <= GB_ACC, "one wave folds a workgroup's records");
     extern __shared__ __attribute__((aligned(16))) uint4 gb_lds[];
-    uint4 *const TL = gb_lds, *const T1 = gb_lds + GB_TAB, *const acc = gb_lds + 2 * GB_TAB;
+    uint4 *const TL = gb_lds, *const T1 = gb_lds + GF_TAB, *const acc = gb_lds + 2 * GF_TAB;
     uint32_t *const jst = (uint32_t *)(acc + GB_ACC);
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t rec = tid / L, l = tid % L; /* the record of the group this lane works on, and its lane there */
-    const uint4 *gl = P.tab + (L == 16 ? 0 : GB_TAB), *g1 = P.tab + 2 * GB_TAB;
-    for (uint32_t i = tid; i < GB_TAB; i += 64 * GB_WAVES) {
+    const uint4 *gl = P.tab + (L == 16 ? 0 : GF_TAB), *g1 = P.tab + 2 * GF_TAB;
+    for (uint32_t i = tid; i < GF_TAB; i += 64 * GB_WAVES) {
         TL[i] = ld_u4<false, true>(gl + i);
         T1[i] = ld_u4<false, true>(g1 + i);
     }
@@ -302,17 +256,7 @@ __global__ __launch_bounds__(64 * WIPE_WAVES) void k_gcm_batch_wipe(const otc_gc
 hipError_t gb_opt_in()
 {
     static_assert(GB_LANES_SHORT == 16 && GB_LANES_LONG == 64, "the two instantiations below");
-    static std::atomic<uint64_t> opted{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (opted.load(std::memory_order_acquire) & bit) return hipSuccess;
-    e = hipFuncSetAttribute((const void *)k_ghash_batch<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GB_LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)k_ghash_batch<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GB_LDS);
-    if (e == hipSuccess) opted.fetch_or(bit, std::memory_order_acq_rel);
-    return e;
+    return otc_dev::lds_opt_in<k_ghash_batch<16>, k_ghash_batch<64>>(GB_LDS);
 }
 
 } // namespace
@@ -328,14 +272,14 @@ int gcm_batch_spans(uint64_t *spans, int max)
     return n;
 }
 
-size_t gcm_batch_table_bytes() { return (size_t)GB_NTAB * GB_TAB * 16; }
+size_t gcm_batch_table_bytes() { return (size_t)GB_NTAB * GF_TAB * 16; }
 
 hipError_t gcm_batch_tables(const uint8_t h[16], void *tab, hipStream_t st)
 {
     /* here, not at the first run: a run may be inside a stream capture */
     hipError_t e = gb_opt_in();
     if (e != hipSuccess) return e;
-    GbConsts K{};
+    GfConsts<GB_NTAB> K{}; /* H^16, H^64, H */
     uint8_t c[16];
     memcpy(c, h, 16);
     memcpy(&K.c[2], c, 16);
@@ -343,7 +287,7 @@ hipError_t gcm_batch_tables(const uint8_t h[16], void *tab, hipStream_t st)
     memcpy(&K.c[0], c, 16);
     for (int i = 0; i < 2; ++i) aes_gf128_mul(c, c, c); /* H^64 */
     memcpy(&K.c[1], c, 16);
-    hipLaunchKernelGGL(k_gcm_batch_tables, dim3(GB_NTAB * 16), dim3(256), 0, st, K, (uint4 *)tab);
+    hipLaunchKernelGGL(k_gf128_tables<GB_NTAB>, dim3(GB_NTAB * 16), dim3(256), 0, st, K, (uint4 *)tab);
     return hipGetLastError();
 }
 

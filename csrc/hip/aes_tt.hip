@@ -36,7 +36,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -924,16 +923,8 @@ inline int num_cus() { return otc_dev::device_cus(); }
 template <auto KERN, typename... A>
 hipError_t launch_dyn(dim3 g, dim3 b, uint32_t lds, hipStream_t st, A... args)
 {
-    static std::atomic<uint64_t> opted{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = otc_dev::lds_opt_in<KERN>(lds);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(opted.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        opted.fetch_or(bit, std::memory_order_acq_rel);
-    }
     hipLaunchKernelGGL(KERN, g, b, lds, st, args...);
     return hipGetLastError();
 }

@@ -67,7 +67,6 @@
 
 namespace otc_impl {
 
-using otc_dev::alloc_fault;
 using otc_dev::lane_id;
 using otc_dev::ld_u4;
 using otc_dev::st_u4;
@@ -431,29 +430,8 @@ __global__ __launch_bounds__(64) void k_poly1305_final(PlFinal F)
 
 uint32_t ld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
-/* blocks and spans of every level over nbytes of data */
-struct PlPlan {
-    int nlevels;
-    uint64_t nblocks[PL_MAX_LEVELS], nspans[PL_MAX_LEVELS];
-    size_t bytes; /* every level's partials */
-};
-bool pl_plan(uint64_t nbytes, PlPlan &pl)
-{
-    pl.nlevels = 0;
-    pl.bytes = 0;
-    if (nbytes > UINT64_MAX - 15) return false;
-    uint64_t n = (nbytes + 15) / 16;
-    while (n) {
-        if (pl.nlevels == PL_MAX_LEVELS) return false;
-        const uint64_t sp = (n + PL_SPAN - 1) / PL_SPAN;
-        pl.nblocks[pl.nlevels] = n;
-        pl.nspans[pl.nlevels] = sp;
-        pl.bytes += (size_t)sp * PL_ENTRY;
-        ++pl.nlevels;
-        n = sp > 1 ? sp : 0;
-    }
-    return true;
-}
+/* the workspace: every level's partials */
+constexpr otc_dev::HashShape PL_SHAPE{PL_SPAN, PL_BATCH, PL_WAVES, PL_MAX_LEVELS, PL_ENTRY, 0};
 
 } // namespace
 
@@ -489,35 +467,16 @@ hipError_t chacha20_run(const void *in, void *out, uint64_t nbytes, const uint8_
     return hipSuccess;
 }
 
-int poly1305_spans(uint64_t *spans, int max)
-{
-    const uint64_t all[] = {64 * 16ull,                           /* a pass */
-                            PL_BATCH * 64 * 16ull,                /* a batch of passes */
-                            PL_SPAN * 16ull,                      /* a wave span */
-                            (uint64_t)PL_WAVES * PL_SPAN * 16,    /* a workgroup's spans */
-                            (uint64_t)PL_SPAN * PL_SPAN * 16,     /* a level-2 span */
-                            (uint64_t)PL_SPAN * PL_SPAN * PL_SPAN * 16};
-    const int n = (int)(sizeof all / sizeof all[0]);
-    for (int i = 0; i < n && i < max; ++i) spans[i] = all[i];
-    return n;
-}
+int poly1305_spans(uint64_t *spans, int max) { return otc_dev::hash_spans(PL_SHAPE, spans, max); }
 
-hipError_t poly1305_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws)
-{
-    *ws = nullptr;
-    PlPlan pl;
-    if (!pl_plan(nbytes, pl)) return hipErrorInvalidValue;
-    if (pl.nlevels == 0) return hipSuccess;
-    if (alloc_fault()) return hipErrorOutOfMemory;
-    return otc_dev::ws_alloc(ws, pl.bytes, st);
-}
+hipError_t poly1305_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws) { return otc_dev::hash_ws_alloc(PL_SHAPE, nbytes, st, ws); }
 
 hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], const uint32_t h0[5],
                         const uint8_t s[16], const uint8_t *lenblock, bool pad16, void *out16, void *ws,
                         hipStream_t st)
 {
-    PlPlan pl;
-    if (!pl_plan(nbytes, pl) || (pl.nlevels && !ws)) {
+    otc_dev::HashLevels pl;
+    if (!otc_dev::hash_levels(PL_SHAPE, nbytes, pl) || (pl.nlevels && !ws)) {
         if (ws) (void)otc_dev::ws_free(ws, st);
         return hipErrorInvalidValue;
     }

@@ -1,7 +1,9 @@
 /*
  * engine_internal.h -- helpers shared by the host runtime translation units
- * (engine.cpp: device ops / keys / info; split.cpp: kernel choice and the
- * claimed runs; pipeline.cpp: host streaming engine and multi-GPU jobs).
+ * (engine.cpp: errors, keys, the AES modes and the stream ops; aead.cpp:
+ * GHASH, GCM, ChaCha20-Poly1305 and batched GCM; runtime.cpp: workspaces,
+ * devices, streams, memory, timing; split.cpp: kernel choice and the claimed
+ * runs; pipeline.cpp: host streaming engine and multi-GPU jobs).
  * Not part of the public C API (otc.h).
  */
 #ifndef OTC_ENGINE_INTERNAL_H
@@ -30,6 +32,38 @@ int hip_fail(hipError_t e, const char *what);
 using otc_dev::ctr_from_bytes;
 Ctr128 ctr_add(Ctr128 c, uint64_t n, bool wrap64);
 int check_key(const otc_aes_key *k, int dir);
+
+/* ---- engine.cpp: what the AEAD ops share with the AES modes -------------- */
+/* device buffers: non-null, 16-byte aligned, the same (where inplace_ok) or disjoint */
+int check_bufs(const void *in, const void *out, size_t nbytes, bool inplace_ok, const char *what);
+/* CTR with GCM's counter (the low 32 bits wrap): otc_aes_ctr32 without its roctx range */
+int ctr32_run(const void *in, void *out, size_t nbytes, const otc_aes_key *k, const uint8_t ctr0[16], int impl,
+              void *stream);
+/* the kernel family of the calling thread's last AES call (otc_last_impl) */
+void set_last_impl(int impl);
+
+/* [a, a + n) and [b, b + n) intersect without being the same range */
+inline bool partial_overlap(const void *a, const void *b, size_t n)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x != y && x < y + n && y < x + n;
+}
+
+/* v as 8 big-endian bytes */
+inline void store_be64(uint8_t *p, uint64_t v)
+{
+    for (int i = 0; i < 8; ++i) p[i] = (uint8_t)(v >> (56 - 8 * i));
+}
+
+/* the batched kernels' tile sizes in blocks; a batch's tile map: record m owns the nt tiles from t on (returns t + nt) */
+inline bool check_tile_blocks(int tile_blocks) { return tile_blocks == 64 || tile_blocks == 128 || tile_blocks == 256; }
+inline uint64_t tile_map_fill(uint32_t *tile_msg, uint64_t *tile_first, size_t m, uint64_t t, uint64_t nt)
+{
+    if (tile_first) tile_first[m] = t;
+    if (tile_msg)
+        for (uint64_t k = 0; k < nt; ++k) tile_msg[t + k] = (uint32_t)m;
+    return t + nt;
+}
 
 /* ---- split.cpp: which kernels a call runs, and the claimed runs ---------- */
 int check_impl(int impl);

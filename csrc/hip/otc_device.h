@@ -152,9 +152,6 @@ struct SplitClaim {
     uint32_t pb = 0;         /* units [nunits - pb, nunits): the T-table waves' first units, unclaimed */
 };
 
-/* lane id from the exec-mask count: nothing to keep live across a loop
- * (threadIdx.x lives in v0 from kernel entry; read in every trip of a long
- * loop body, hipcc keeps it -- and spills it) */
 /* 16-byte global load / store with an optional non-temporal hint (the NT
  * bit: the line is not kept in L2 / MALL).  Streaming data that is read once
  * and written once -- every byte of a 64 GiB CTR call -- does not benefit
@@ -198,6 +195,9 @@ __device__ __forceinline__ void st_u4(void *p, uint4 v)
     }
 }
 
+/* lane id from the exec-mask count: nothing to keep live across a loop
+ * (threadIdx.x lives in v0 from kernel entry; read in every trip of a long
+ * loop body, hipcc keeps it -- and spills it) */
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 /* one atomic add of `inc` on the claim word; returns the old value (wave-uniform) */
@@ -309,6 +309,75 @@ hipError_t ws_alloc(void **p, size_t bytes, hipStream_t st);
 hipError_t ws_free(void *p, hipStream_t st);
 void ws_release_all();
 
+/* The level decomposition that the two chip-wide hashes share, host side
+ * (GHASH in aes_gcm.hip, Poly1305 in chacha.hip): n blocks are cut into wave
+ * spans of `span` blocks, whose partials the same kernel hashes again, level
+ * after level, until one block is left.  The spans are aligned to the END of
+ * the data: the first one is the short one (zero blocks in front of the data
+ * change nothing), every later one full.  What differs is in HashShape; the
+ * kernels and their per-level parameters stay with each hash. */
+constexpr int HASH_MAX_LEVELS = 4; /* the most any shape asks for */
+struct HashShape {
+    uint32_t span;        /* blocks of a wave span: 64 lanes x the blocks per lane */
+    uint32_t batch;       /* passes of 64 blocks that the kernel takes at a time */
+    uint32_t waves;       /* wave spans of a workgroup */
+    int max_levels;       /* span^max_levels blocks are the most a call may have */
+    size_t partial_bytes; /* bytes of one span's partial in the workspace */
+    size_t level_bytes;   /* bytes a level needs besides its partials (tables) */
+};
+
+/* blocks and spans of every level over nbytes of data */
+struct HashLevels {
+    int nlevels; /* 0: no data */
+    uint64_t nblocks[HASH_MAX_LEVELS], nspans[HASH_MAX_LEVELS];
+    size_t bytes; /* of the workspace: every level's extra bytes, then every level's partials */
+};
+
+/* false: more data than the shape's levels reach */
+inline bool hash_levels(const HashShape &s, uint64_t nbytes, HashLevels &pl)
+{
+    pl.nlevels = 0;
+    pl.bytes = 0;
+    if (nbytes > UINT64_MAX - 15) return false;
+    uint64_t n = (nbytes + 15) / 16;
+    while (n) {
+        if (pl.nlevels == s.max_levels || pl.nlevels == HASH_MAX_LEVELS) return false;
+        const uint64_t sp = (n + s.span - 1) / s.span;
+        pl.nblocks[pl.nlevels] = n;
+        pl.nspans[pl.nlevels] = sp;
+        pl.bytes += (size_t)sp * s.partial_bytes;
+        ++pl.nlevels;
+        n = sp > 1 ? sp : 0;
+    }
+    pl.bytes += (size_t)pl.nlevels * s.level_bytes;
+    return true;
+}
+
+/* byte sizes of the decomposition's pieces, smallest first; returns how many there are */
+inline int hash_spans(const HashShape &s, uint64_t *spans, int max)
+{
+    const uint64_t all[] = {64 * 16ull,                           /* a pass */
+                            s.batch * 64 * 16ull,                 /* a batch of passes */
+                            s.span * 16ull,                       /* a wave span */
+                            (uint64_t)s.waves * s.span * 16,      /* a workgroup's spans */
+                            (uint64_t)s.span * s.span * 16,       /* a level-2 span */
+                            (uint64_t)s.span * s.span * s.span * 16};
+    const int n = (int)(sizeof all / sizeof all[0]);
+    for (int i = 0; i < n && i < max; ++i) spans[i] = all[i];
+    return n;
+}
+
+/* one call's workspace, behind otc_fault_inject_alloc; *ws stays null for nbytes == 0 */
+inline hipError_t hash_ws_alloc(const HashShape &s, uint64_t nbytes, hipStream_t st, void **ws)
+{
+    *ws = nullptr;
+    HashLevels pl;
+    if (!hash_levels(s, nbytes, pl)) return hipErrorInvalidValue;
+    if (pl.nlevels == 0) return hipSuccess;
+    if (alloc_fault()) return hipErrorOutOfMemory;
+    return ws_alloc(ws, pl.bytes, st);
+}
+
 /* Host: CU count of the calling thread's current device, cached per device.
  * Thread-safe (the multi-GPU paths launch from one host thread per GPU): the
  * attribute is immutable, so a relaxed atomic cache is enough. */
@@ -324,6 +393,23 @@ inline int device_cus()
         slot.store(v, std::memory_order_relaxed);
     }
     return v;
+}
+
+/* Host: the opt-in to more than 64 KiB of dynamic LDS for all of KERNS, once
+ * per device: one bit per device in a word of this instantiation, set only
+ * after every kernel has taken the attribute. */
+template <auto... KERNS>
+hipError_t lds_opt_in(uint32_t lds_bytes)
+{
+    static std::atomic<uint64_t> opted{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (e != hipSuccess || (opted.load(std::memory_order_acquire) & bit)) return e;
+    for (const void *k : {(const void *)KERNS...})
+        if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)) != hipSuccess) return e;
+    opted.fetch_or(bit, std::memory_order_acq_rel);
+    return hipSuccess;
 }
 
 } // namespace otc_dev

@@ -1,7 +1,8 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip, stream_ops.hip), declared once: included by their callers
- * (engine.cpp, split.cpp) and by the files that define them, so every
+ * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
+ * stream_ops.hip), declared once: included by their callers (engine.cpp,
+ * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
  * of the public C API (otc.h).
  */

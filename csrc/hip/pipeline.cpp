@@ -137,10 +137,7 @@ static int check_stream_args(int mode, const void *host_in, const void *host_out
     } else if (int r = check_key(k, k->dir)) {
         return r;
     }
-    if (host_in != host_out && nbytes) {
-        const uintptr_t a = (uintptr_t)host_in, b = (uintptr_t)host_out;
-        if (a < b + nbytes && b < a + nbytes) return set_err(OTC_ERR_ARG, "input and output overlap partially");
-    }
+    if (partial_overlap(host_in, host_out, nbytes)) return set_err(OTC_ERR_ARG, "input and output overlap partially");
     return OTC_OK;
 }
 

@@ -671,7 +671,7 @@ def test_persistent_ttable_ctr(gpu, bits):
 def test_persistent_ttable_midsize(gpu):
     """ECB (both directions), CBC / CFB decryption and their segment forms
     between 896 MiB and 2 GiB run the persistent T-table claim kernel alone
-    (engine.cpp split_form FORM_TT): equal to the bitsliced claim kernel alone
+    (split.cpp split_form FORM_TT): equal to the bitsliced claim kernel alone
     and, on samples, to the oracle -- a size with a partial last unit, so
     workgroup 0's remainder path runs too."""
     key, iv = os.urandom(32), os.urandom(16)
