@@ -9,14 +9,11 @@ family: ``last_impl`` / ``pick_impl`` do not know these ops.
 """
 from __future__ import annotations
 
-import ctypes
-import hmac
-
 import torch
 
 from .. import _native
 from ..models.cpu_ref import CHACHA_MAX_BYTES, ChaChaTagError, _chacha_args, chacha_check_counter
-from .aes_ops import _bytes, _check_dev, _lib, _nbytes, _out_like, _run, _stream
+from ._common import _aligned, _call, _check_dev, _lib, _nbytes, _open_with_tag, _out_like, _spans, _stream
 from .keys import DECRYPT, ENCRYPT
 
 
@@ -24,6 +21,7 @@ def chacha20(x: torch.Tensor, key: bytes, nonce: bytes, counter: int = 0, out: t
     """``x`` XOR the ChaCha20 keystream from block ``counter``.  Any byte
     length and any alignment (buffers that are not 16-byte aligned run on the
     slower byte-wise kernel); may run in place."""
+    # written out, not through _call: the native op takes any alignment, so nothing is staged
     _check_dev(x, "x")
     key, nonce = _chacha_args(key, nonce)
     n = _nbytes(x)
@@ -45,11 +43,9 @@ def poly1305(x: torch.Tensor, key: bytes) -> torch.Tensor:
     if len(key) != 32:
         raise ValueError("a Poly1305 key has 32 bytes")
     tag = torch.empty(16, dtype=torch.uint8, device=x.device)
-    xb = _bytes(x)
-    if xb.data_ptr() % 16 and xb.numel():
-        xb = xb.clone()  # the kernel loads 16 bytes per lane
+    xb = _aligned(x)  # the kernel loads 16 bytes per lane
     with torch.cuda.device(x.device):
-        rc = _lib().otc_poly1305(xb.data_ptr(), xb.numel(), _native.as_u8p(key), tag.data_ptr(), _stream(x))
+        rc = _lib().otc_poly1305(xb.data_ptr(), _nbytes(x), _native.as_u8p(key), tag.data_ptr(), _stream(x))
     _native.check(rc, "otc_poly1305")
     return tag
 
@@ -58,9 +54,7 @@ def poly1305_spans() -> list[int]:
     """Byte sizes of the pieces the Poly1305 kernel cuts its data into,
     smallest first (otc.h otc_poly1305_spans): lengths around them take
     different paths."""
-    buf = (ctypes.c_uint64 * 16)()
-    n = _lib().otc_poly1305_spans(buf, 16)
-    return [int(v) for v in buf[:n]]
+    return _spans("otc_poly1305_spans")
 
 
 def _aead(x: torch.Tensor, key: bytes, nonce: bytes, aad: bytes, out, decrypt: bool):
@@ -72,11 +66,9 @@ def _aead(x: torch.Tensor, key: bytes, nonce: bytes, aad: bytes, out, decrypt: b
         raise ValueError("a ChaCha20-Poly1305 message has at most (2**32 - 1) * 64 bytes")
     out = _out_like(x, out)
     tag = torch.empty(16, dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _run(x, out, lambda ip, op: _lib().otc_chacha20_poly1305(
-            ip, op, n, _native.as_u8p(key), DECRYPT if decrypt else ENCRYPT, _native.as_u8p(nonce),
-            _native.as_u8p(aad), len(aad), tag.data_ptr(), _stream(x)))
-    _native.check(rc, "otc_chacha20_poly1305")
+    _call("otc_chacha20_poly1305", x, out, lambda ip, op: (
+        ip, op, n, _native.as_u8p(key), DECRYPT if decrypt else ENCRYPT, _native.as_u8p(nonce),
+        _native.as_u8p(aad), len(aad), tag.data_ptr(), _stream(x)))
     return out, tag
 
 
@@ -94,11 +86,6 @@ def chacha20_poly1305_decrypt(c: torch.Tensor, key: bytes, nonce: bytes, tag, aa
     only synchronisation -- and compared in constant time.  On a mismatch
     ``out`` is zeroed and ``ChaChaTagError`` (a ``ValueError``) raised.  May
     run in place."""
-    tag = bytes(tag.cpu().numpy().tobytes()) if isinstance(tag, torch.Tensor) else bytes(tag)
-    if len(tag) != 16:
-        raise ValueError("a ChaCha20-Poly1305 tag has 16 bytes")
-    out, t = _aead(c, key, nonce, aad, out, True)
-    if not hmac.compare_digest(t.cpu().numpy().tobytes(), tag):
-        out.zero_()
-        raise ChaChaTagError("ChaCha20-Poly1305 tag mismatch: the output was zeroed")
-    return out
+    return _open_with_tag(tag, (16,), "a ChaCha20-Poly1305 tag has 16 bytes",
+                          lambda: _aead(c, key, nonce, aad, out, True),
+                          ChaChaTagError, "ChaCha20-Poly1305 tag mismatch: the output was zeroed")

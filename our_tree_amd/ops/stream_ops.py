@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from .. import _native
-from .aes_ops import _bytes, _check_dev, _nbytes, _run, _stream
+from ._common import _aligned, _call, _check_dev, _check_out, _lib, _nbytes, _out_like, _stream
 
 
 def xor(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -16,14 +16,11 @@ def xor(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> to
     _check_dev(b, "b")
     if _nbytes(a) != _nbytes(b):
         raise ValueError("a and b must have the same byte size")
-    out = torch.empty_like(a) if out is None else out
-    if b.data_ptr() % 16:
-        b = _bytes(b).clone()  # 16-byte alignment (a and out are staged by _run)
-    with torch.cuda.device(a.device):
-        rc = _run(a, out, lambda ip, op: _native.require_gpu_lib().otc_xor(
-            ip, b.data_ptr(), op, _nbytes(a), _stream(a)))
-    _native.check(rc, "otc_xor")
-    return out
+    if b.device != a.device:
+        raise ValueError(f"b must be on a's device (b is on {b.device}, a on {a.device})")
+    out = _out_like(a, out)
+    bb = _aligned(b)  # 16-byte alignment (a and out are staged by _run)
+    return _call("otc_xor", a, out, lambda ip, op: (ip, bb.data_ptr(), op, _nbytes(a), _stream(a)))
 
 
 def rc4_multi(keys: torch.Tensor, length: int, x: torch.Tensor | None = None, drop: int = 0,
@@ -40,11 +37,15 @@ def rc4_multi(keys: torch.Tensor, length: int, x: torch.Tensor | None = None, dr
         _check_dev(x, "x")
         if _nbytes(x) != ns * length:
             raise ValueError("x must hold nstreams*length bytes")
-    out = torch.empty((ns, length), dtype=torch.uint8, device=keys.device) if out is None else out
-    with torch.cuda.device(keys.device):
-        rc = _native.require_gpu_lib().otc_rc4_multi(keys.data_ptr(), kl, ns, length, drop,
-                                                     x.data_ptr() if x is not None else None, out.data_ptr(),
-                                                     _stream(keys))
+        if x.device != keys.device:
+            raise ValueError(f"x must be on keys' device (x is on {x.device}, keys on {keys.device})")
+    if out is None:
+        out = torch.empty((ns, length), dtype=torch.uint8, device=keys.device)
+    else:
+        _check_out(out, ns * length, keys.device, "out must hold nstreams*length bytes")
+    with torch.cuda.device(keys.device):  # no _call: the kernel reads and writes bytes, nothing is staged
+        rc = _lib().otc_rc4_multi(keys.data_ptr(), kl, ns, length, drop, x.data_ptr() if x is not None else None,
+                                  out.data_ptr(), _stream(keys))
     _native.check(rc, "otc_rc4_multi")
     return out
 
@@ -78,37 +79,28 @@ def rc4_crypt_batch(states: torch.Tensor, x: torch.Tensor, out: torch.Tensor | N
     if ns == 0 or _nbytes(x) % ns:
         raise ValueError("x must hold nstreams * len bytes")
     length = _nbytes(x) // ns
-    out = torch.empty_like(x) if out is None else out
-    _check_dev(out, "out")
-    if _nbytes(out) != _nbytes(x):
-        raise ValueError("out must have the byte size of x")
-    if not (states.device == x.device == out.device):
-        raise ValueError(f"states, x and out must be on one device (got {states.device}, {x.device}, {out.device})")
-    with torch.cuda.device(x.device):
-        rc = _native.require_gpu_lib().otc_rc4_crypt_batch(states.data_ptr(), ns, length, x.data_ptr(),
-                                                           out.data_ptr(), _stream(x))
+    out = _out_like(x, out)
+    if states.device != x.device:
+        raise ValueError(f"states must be on x's device (states is on {states.device}, x on {x.device})")
+    with torch.cuda.device(x.device):  # no _call: the kernel reads and writes bytes, nothing is staged
+        rc = _lib().otc_rc4_crypt_batch(states.data_ptr(), ns, length, x.data_ptr(), out.data_ptr(), _stream(x))
     _native.check(rc, "otc_rc4_crypt_batch")
     return out
 
 
 def fill_random_(t: torch.Tensor, seed: int = 0) -> torch.Tensor:
     """Fill ``t`` in place with deterministic pseudo-random bytes (splitmix64)."""
-    _check_dev(t, "t")
-    with torch.cuda.device(t.device):
-        rc = _run(t, t, lambda ip, op: _native.require_gpu_lib().otc_fill_random(
-            op, _nbytes(t), seed & (2**64 - 1), _stream(t)))
-    _native.check(rc, "otc_fill_random")
-    return t
+    _check_dev(t, "t")  # its own out
+    return _call("otc_fill_random", t, t, lambda ip, op: (op, _nbytes(t), seed & (2**64 - 1), _stream(t)))
 
 
 def checksum(t: torch.Tensor) -> int:
     """Position-dependent 64-bit XOR fold of a device buffer (byte size % 8 == 0)."""
     _check_dev(t, "t")
     acc = torch.zeros(1, dtype=torch.int64, device=t.device)
-    if t.data_ptr() % 8:
-        t = _bytes(t).clone()  # the fold reads 8-byte words
+    t = _aligned(t, 8)  # the fold reads 8-byte words
     with torch.cuda.device(t.device):
-        rc = _native.require_gpu_lib().otc_checksum(t.data_ptr(), _nbytes(t), acc.data_ptr(), _stream(t))
+        rc = _lib().otc_checksum(t.data_ptr(), _nbytes(t), acc.data_ptr(), _stream(t))
     _native.check(rc, "otc_checksum")
     return int(acc.item()) & (2**64 - 1)
 
@@ -121,8 +113,7 @@ def clock_probe(delay_s: float, window_s: float, device=None, stream=None) -> to
     out = torch.zeros(2, dtype=torch.int64, device=dev)
     s = stream if stream is not None else torch.cuda.Stream(device=dev)
     with torch.cuda.device(dev):
-        rc = _native.require_gpu_lib().otc_clock_probe(out.data_ptr(), float(delay_s), float(window_s),
-                                                       ctypes.c_void_p(s.cuda_stream))
+        rc = _lib().otc_clock_probe(out.data_ptr(), float(delay_s), float(window_s), ctypes.c_void_p(s.cuda_stream))
     _native.check(rc, "otc_clock_probe")
     out._probe_stream = s  # keep the side stream alive until the result is read
     return out

@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 
 from .. import _native
-from ..ops.aes_ops import _impl
+from ..ops._common import _impl
 from ..ops.keys import expand_key
 
 MODES = {"ecb": 0, "ctr": 1, "cbc-dec": 2}

@@ -153,7 +153,7 @@ def test_ctr_batch_planner_and_python_plan_agree(lib):
     builds with numpy: 4 KiB tiles, empty messages own none."""
     import numpy as np
 
-    from our_tree_amd.ops import aes_ops
+    from our_tree_amd.ops import batch_ops
 
     sizes = [0, 1, 4096, 4097, 16, 0, 3 * 4096 + 15, 100000, 1504]
     msgs = (CtrMsg * len(sizes))(*[CtrMsg(0, 0, n, 0, 0, 0, 0) for n in sizes])
@@ -174,8 +174,8 @@ def test_ctr_batch_planner_and_python_plan_agree(lib):
     al = (CtrMsg * 2)(CtrMsg(0, 0, 4096 * 10, 0, 0, 0, 0x80000000 | 5), CtrMsg(0, 0, 4096 * 10, 0, 0, 0, 0x80000000))
     assert fn(al, 2, 256, None, None) == 11 + 10
     # tile choice: 4 KiB messages fill 256-block tiles exactly, 1 KiB ones 64-block tiles
-    assert aes_ops._pick_tile(np.full(100, 4096, np.uint64)) == 256
-    assert aes_ops._pick_tile(np.full(100, 1024, np.uint64)) == 64
+    assert batch_ops._pick_tile(np.full(100, 4096, np.uint64)) == 256
+    assert batch_ops._pick_tile(np.full(100, 1024, np.uint64)) == 64
 
 
 def test_ctr_batch_rejects_bad_launch_args(lib):
