@@ -37,14 +37,14 @@ OBJ    := build/obj
 
 CPU_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/rc4.c csrc/cpu/aesni.c csrc/cpu/numa.c csrc/cpu/rccl_plan.c csrc/cpu/chacha.c
 CPU_OBJ := $(patsubst csrc/cpu/%.c,$(OBJ)/cpu/%.o,$(CPU_SRC)) $(OBJ)/cpu/bs_selftest.o
-HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/stream_ops.hip
+HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/chacha_batch.hip csrc/hip/stream_ops.hip
 HIP_OBJ := $(patsubst csrc/hip/%.hip,$(OBJ)/hip/%.o,$(HIP_SRC)) $(OBJ)/hip/engine.o $(OBJ)/hip/aead.o $(OBJ)/hip/runtime.o $(OBJ)/hip/split.o $(OBJ)/hip/pipeline.o
 
 BINS := bin/test bin/aes_test bin/aes_ecb_e bin/aes_ecb_d bin/otbench bin/bc_test
 
 .PHONY: all cpu clean
-all: $(LIBDIR)/libotc.so $(LIBDIR)/libotc_cpu.so $(BINS) bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim ref-o0
-cpu: $(LIBDIR)/libotc_cpu.so bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim ref-o0
+all: $(LIBDIR)/libotc.so $(LIBDIR)/libotc_cpu.so $(BINS) bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest ref-o0
+cpu: $(LIBDIR)/libotc_cpu.so bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest ref-o0
 
 $(OBJ)/cpu/aesni.o: csrc/cpu/aesni.c csrc/include/aesni.h
 	@mkdir -p $(dir $@)
@@ -114,6 +114,13 @@ bin/otbench_hostsim: csrc/cli/otbench.cpp csrc/cli/otc_hostsim.cpp $(CPU_OBJ)
 	@mkdir -p bin
 	$(CXX) -O2 -std=c++17 -Wall $(INC) csrc/cli/otbench.cpp csrc/cli/otc_hostsim.cpp $(CPU_OBJ) -o $@ -lpthread
 
+# the batched Poly1305 kernel's decomposition on the host, with the kernel's own
+# arithmetic (csrc/hip/chacha_dev.h), against chacha.c (tests/test_chacha_batch_cpu.py
+# also builds it with -fsanitize=address,undefined)
+bin/poly_batch_selftest: csrc/cpu/poly_batch_selftest.cpp csrc/hip/chacha_dev.h $(OBJ)/cpu/chacha.o
+	@mkdir -p bin
+	$(CXX) -O2 -g -std=c++17 -Wall -Wno-unknown-pragmas $(INC) $< $(OBJ)/cpu/chacha.o -o $@ $(SANLD)
+
 bin/bc_test: csrc/cli/bc_test.cpp csrc/include/otc_cipher.hpp $(LIBDIR)/libotc.so
 	@mkdir -p bin
 	$(CXX) -O2 -std=c++17 -Wall $(INC) $< -o $@ -L$(LIBDIR) -lotc -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
@@ -159,7 +166,7 @@ bin/aes_test_o0: csrc/cli/aes_test.c $(O0_OBJ)
 	$(CXX) -O0 -g $(INC) -x c -std=gnu99 $< -x none $(O0_OBJ) -o $@ -lpthread
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
+	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/poly_batch_selftest bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
 
 # Host sanitizers over the threaded CPU paths (also tests/test_sanitizers_cpu.py)
 SAN_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/chacha.c csrc/cli/san_driver.c

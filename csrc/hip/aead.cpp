@@ -1,8 +1,9 @@
 /*
  * aead.cpp -- the hash and authenticated-encryption ops of the C API (otc.h):
  * GHASH and AES-GCM (counter mode: engine.cpp's ctr32_run; hash: aes_gcm.hip),
- * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), and batched GCM
- * (aes_gcm_batch.hip and the batched CTR kernel): the argument checks, what an
+ * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), batched GCM
+ * (aes_gcm_batch.hip and the batched CTR kernel) and batched
+ * ChaCha20-Poly1305 (chacha_batch.hip): the argument checks, what an
  * op computes on the host (J0, the AAD's hash, the one-time key, the length
  * blocks) and the order of its launches.
  */
@@ -215,6 +216,54 @@ extern "C" int otc_chacha20_poly1305(const void *in, void *out, size_t nbytes, c
     return OTC_OK;
 }
 
+/* ---- what the two batched AEADs' planners share ----------------------------- */
+/* One record's buffers as otc_gcm_msg and otc_chacha_msg both hold them (in,
+ * out, nbytes, aad, aad_bytes): what is wrong with them, or null. */
+template <class Msg>
+static const char *batch_record_fault(const Msg &d, uint64_t max_bytes, uint64_t max_aad, const char *too_big)
+{
+    if (d.nbytes > max_bytes) return too_big;
+    if (d.aad_bytes > max_aad) return "more than 64 KiB of AAD";
+    if (d.aad_bytes && !d.aad) return "null aad";
+    if (!d.nbytes) return nullptr;
+    if (!d.in || !d.out) return "null buffer";
+    if ((d.in | d.out) & 15u) return "data buffers must be 16-byte aligned";
+    if (partial_overlap((const void *)d.in, (const void *)d.out, d.nbytes)) return "input and output overlap partially";
+    return nullptr;
+}
+
+/* The three checks across records: no two outputs share bytes, no record reads
+ * what another writes, no AAD lies in any output.  0, or bad(record, what). */
+template <class Msg, class Bad>
+static int batch_overlaps(const Msg *msgs, size_t nmsg, Bad bad)
+{
+    struct Iv {
+        uint64_t lo, hi;
+        size_t m;
+    };
+    std::vector<Iv> outs; /* the non-empty outputs, to find records that overlap */
+    for (size_t m = 0; m < nmsg; ++m)
+        if (msgs[m].nbytes) outs.push_back({msgs[m].out, msgs[m].out + msgs[m].nbytes, m});
+    std::sort(outs.begin(), outs.end(), [](const Iv &a, const Iv &b) { return a.lo < b.lo; });
+    for (size_t i = 1; i < outs.size(); ++i)
+        if (outs[i].lo < outs[i - 1].hi) return bad(outs[i].m, "its output overlaps another record's");
+    for (size_t m = 0; m < nmsg; ++m) { /* no record reads what another writes */
+        const Msg &d = msgs[m];
+        if (!d.nbytes) continue;
+        auto it = std::upper_bound(outs.begin(), outs.end(), d.in,
+                                   [](uint64_t a, const Iv &o) { return a < o.hi; }); /* first output ending past in */
+        for (; it != outs.end() && it->lo < d.in + d.nbytes; ++it)
+            if (it->m != m) return bad(m, "its input overlaps another record's output");
+    }
+    for (size_t m = 0; m < nmsg; ++m) { /* an encryption writes every output before the hash reads the AADs */
+        const Msg &d = msgs[m];
+        if (!d.aad_bytes) continue;
+        auto it = std::upper_bound(outs.begin(), outs.end(), d.aad, [](uint64_t a, const Iv &o) { return a < o.hi; });
+        if (it != outs.end() && it->lo < d.aad + d.aad_bytes) return bad(m, "its AAD overlaps a record's output");
+    }
+    return 0;
+}
+
 /* ---- batched GCM: many records, own IVs, one tag array --------------------- */
 extern "C" int otc_gcm_batch_spans(uint64_t *spans, int max) { return otc_impl::gcm_batch_spans(spans, spans ? max : 0); }
 
@@ -245,41 +294,12 @@ extern "C" int64_t otc_gcm_batch_plan(const otc_gcm_msg *msgs, size_t nmsg, int 
     auto bad = [](size_t m, const char *what) {
         return set_err(OTC_ERR_ARG, "gcm_batch: record " + std::to_string(m) + ": " + what);
     };
-    struct Iv {
-        uint64_t lo, hi;
-        size_t m;
-    };
-    std::vector<Iv> outs; /* the non-empty outputs, to find records that overlap */
-    for (size_t m = 0; m < nmsg; ++m) {
-        const otc_gcm_msg &d = msgs[m];
-        /* at most 65536 blocks: the counter's low 32 bits, started at 2, never wrap */
-        if (d.nbytes > OTC_GCM_BATCH_MAX_BYTES) return bad(m, "more than 1 MiB of data (use otc_aes_gcm)");
-        if (d.aad_bytes > OTC_GCM_BATCH_MAX_AAD) return bad(m, "more than 64 KiB of AAD");
-        if (d.aad_bytes && !d.aad) return bad(m, "null aad");
-        if (!d.nbytes) continue;
-        if (!d.in || !d.out) return bad(m, "null buffer");
-        if ((d.in | d.out) & 15u) return bad(m, "data buffers must be 16-byte aligned");
-        if (partial_overlap((const void *)d.in, (const void *)d.out, d.nbytes))
-            return bad(m, "input and output overlap partially");
-        outs.push_back({d.out, d.out + d.nbytes, m});
-    }
-    std::sort(outs.begin(), outs.end(), [](const Iv &a, const Iv &b) { return a.lo < b.lo; });
-    for (size_t i = 1; i < outs.size(); ++i)
-        if (outs[i].lo < outs[i - 1].hi) return bad(outs[i].m, "its output overlaps another record's");
-    for (size_t m = 0; m < nmsg; ++m) { /* no record reads what another writes */
-        const otc_gcm_msg &d = msgs[m];
-        if (!d.nbytes) continue;
-        auto it = std::upper_bound(outs.begin(), outs.end(), d.in,
-                                   [](uint64_t a, const Iv &o) { return a < o.hi; }); /* first output ending past in */
-        for (; it != outs.end() && it->lo < d.in + d.nbytes; ++it)
-            if (it->m != m) return bad(m, "its input overlaps another record's output");
-    }
-    for (size_t m = 0; m < nmsg; ++m) { /* an encryption writes every output before the hash reads the AADs */
-        const otc_gcm_msg &d = msgs[m];
-        if (!d.aad_bytes) continue;
-        auto it = std::upper_bound(outs.begin(), outs.end(), d.aad, [](uint64_t a, const Iv &o) { return a < o.hi; });
-        if (it != outs.end() && it->lo < d.aad + d.aad_bytes) return bad(m, "its AAD overlaps a record's output");
-    }
+    /* at most 65536 blocks: the counter's low 32 bits, started at 2, never wrap */
+    for (size_t m = 0; m < nmsg; ++m)
+        if (const char *f = batch_record_fault(msgs[m], OTC_GCM_BATCH_MAX_BYTES, OTC_GCM_BATCH_MAX_AAD,
+                                               "more than 1 MiB of data (use otc_aes_gcm)"))
+            return bad(m, f);
+    if (int r = batch_overlaps(msgs, nmsg, bad)) return r;
     const uint64_t tile_bytes = 16ull * (uint64_t)tile_blocks;
     uint64_t t = 0;
     for (size_t m = 0; m < nmsg; ++m) {
@@ -396,3 +416,126 @@ extern "C" int otc_aes_gcm_batch(const otc_gcm_msg *msgs_dev, otc_ctr_msg *ctr_m
     return OTC_OK;
 }
 
+/* ---- batched ChaCha20-Poly1305: many records, own key and nonce each -------- */
+extern "C" int otc_chacha_batch_spans(uint64_t *spans, int max)
+{
+    return otc_impl::chacha_batch_spans(spans, spans ? max : 0);
+}
+
+extern "C" size_t otc_chacha_batch_ws_bytes(size_t nmsg) { return nmsg * 32; /* r (clamped) || s per record */ }
+
+extern "C" int64_t otc_chacha_batch_plan(const otc_chacha_msg *msgs, size_t nmsg, size_t nkeys, uint32_t *tile_msg,
+                                         uint64_t *tile_first)
+{
+    if (nmsg == 0) return 0;
+    if (!msgs) return set_err(OTC_ERR_ARG, "chacha_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "chacha_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "chacha_batch: record " + std::to_string(m) + ": " + what);
+    };
+    /* at most 16384 blocks from counter 1: the 32-bit counter never wraps; an
+     * empty record has a key too (its tag's one-time key comes from it) */
+    for (size_t m = 0; m < nmsg; ++m) {
+        if (msgs[m].key >= nkeys) return bad(m, "key index out of range");
+        if (const char *f = batch_record_fault(msgs[m], OTC_CHACHA_BATCH_MAX_BYTES, OTC_CHACHA_BATCH_MAX_AAD,
+                                               "more than 1 MiB of data (use otc_chacha20_poly1305)"))
+            return bad(m, f);
+    }
+    if (int r = batch_overlaps(msgs, nmsg, bad)) return r;
+    const uint64_t tile_bytes = 4096; /* one pass: 64 blocks of 64 bytes */
+    uint64_t t = 0;
+    for (size_t m = 0; m < nmsg; ++m) t = tile_map_fill(tile_msg, tile_first, m, t, (msgs[m].nbytes + tile_bytes - 1) / tile_bytes);
+    return (int64_t)t;
+}
+
+/* 16 lanes per record for short records, 64 for long ones.  Measured on
+ * uniform batches of 64 MiB with a 13-byte AAD (docs/PERF.md "Batched
+ * ChaCha20-Poly1305", benchmarks/chacha_batch.py --lanes-table), the hash
+ * alone: 16 lanes win at 256 B, 1 KiB and 4 KiB records (18, 66 and 258 hashed
+ * blocks: x3.9, x2.8, x1.6), 64 lanes at 16 KiB and 64 KiB (1026 and 4098
+ * blocks: x1.25, x3.0); the whole encryption agrees at every size.  The
+ * choice changes between 258 and 1026 blocks, and nothing between them was
+ * measured: 512 blocks (8 KiB), their geometric mean, is where the rule puts
+ * it.  GCM's 768 does not carry over: this fold is log2 L cross-lane steps,
+ * not a serial chain of L + 1.  SUPPOSED, not measured: that the MEAN of a
+ * mixed batch decides -- no batch of mixed sizes has been timed.  Records do
+ * not wait for one another across waves here (no workgroup barrier), so one
+ * long record does not switch the whole batch, unlike otc_gcm_batch_lanes. */
+extern "C" int otc_chacha_batch_lanes(const otc_chacha_msg *msgs, size_t nmsg)
+{
+    uint64_t total = 0;
+    for (size_t m = 0; msgs && m < nmsg; ++m) total += (msgs[m].aad_bytes + 15) / 16 + (msgs[m].nbytes + 15) / 16 + 1;
+    return nmsg && total / nmsg > 512 ? otc_impl::CB_LANES_LONG : otc_impl::CB_LANES_SHORT;
+}
+
+/* what otc_poly1305_batch and otc_chacha20_poly1305_batch check alike */
+static int chacha_batch_common(const otc_chacha_msg *msgs_dev, const void *tags_dev, int &lanes)
+{
+    if (lanes == 0) lanes = otc_impl::CB_LANES_LONG;
+    if (lanes != otc_impl::CB_LANES_SHORT && lanes != otc_impl::CB_LANES_LONG)
+        return set_err(OTC_ERR_ARG, "chacha_batch: lanes must be 16 or 64 (0: 64)");
+    if (!msgs_dev || !tags_dev) return set_err(OTC_ERR_ARG, "chacha_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "chacha_batch: misaligned descriptor array");
+    if ((uintptr_t)tags_dev & 15u) return set_err(OTC_ERR_ARG, "chacha_batch: the tag array must be 16-byte aligned");
+    return OTC_OK;
+}
+
+extern "C" int otc_poly1305_batch(const otc_chacha_msg *msgs_dev, size_t nmsg, const uint8_t *otk_dev, void *tags_dev,
+                                  int lanes, void *stream)
+{
+    Range rg("otc_poly1305_batch");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = chacha_batch_common(msgs_dev, tags_dev, lanes)) return r;
+    if (!otk_dev) return set_err(OTC_ERR_ARG, "chacha_batch: null array");
+    if ((uintptr_t)otk_dev & 3u) return set_err(OTC_ERR_ARG, "chacha_batch: misaligned one-time key array");
+    const hipError_t e = otc_impl::poly1305_batch_run(msgs_dev, nmsg, otk_dev, tags_dev, nullptr, nullptr, false, lanes,
+                                                      (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "poly1305_batch launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_chacha20_poly1305_batch(const otc_chacha_msg *msgs_dev, const uint32_t *tile_msg_dev,
+                                           const uint64_t *tile_first_dev, uint64_t ntiles, size_t nmsg,
+                                           const uint8_t *keys_dev, int dir, const uint8_t *nonces_dev, void *tags_dev,
+                                           const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, int lanes,
+                                           void *stream)
+{
+    Range rg("otc_chacha20_poly1305_batch");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = chacha_batch_common(msgs_dev, tags_dev, lanes)) return r;
+    if (!keys_dev || !ws_dev) return set_err(OTC_ERR_ARG, "chacha_batch: null array");
+    if (ntiles && (!tile_msg_dev || !tile_first_dev)) return set_err(OTC_ERR_ARG, "chacha_batch: null tile map");
+    if (((uintptr_t)tile_first_dev & 7u) || ((uintptr_t)tile_msg_dev & 3u) || ((uintptr_t)keys_dev & 3u))
+        return set_err(OTC_ERR_ARG, "chacha_batch: misaligned tile map or key array");
+    if ((uintptr_t)ws_dev & 15u) return set_err(OTC_ERR_ARG, "chacha_batch: the workspace must be 16-byte aligned");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "chacha_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * 16;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * 16 && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "chacha_batch: the expected tags overlap the computed tags or the verdicts");
+    }
+    if (!nonces_dev) return set_err(OTC_ERR_ARG, "chacha_batch: null nonces");
+    hipStream_t st = (hipStream_t)stream;
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+
+    hipError_t e = otc_impl::chacha_batch_prep(msgs_dev, nmsg, keys_dev, nonces_dev, ws_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "chacha_batch prep launch");
+    auto cipher = [&] {
+        return otc_impl::chacha20_batch_run(msgs_dev, keys_dev, nonces_dev, tile_msg_dev, tile_first_dev, ntiles, st);
+    };
+    if (enc && (e = cipher()) != hipSuccess) return hip_fail(e, "chacha_batch cipher launch");
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    e = otc_impl::poly1305_batch_run(msgs_dev, nmsg, ws_dev, tags_dev, enc ? nullptr : expect_dev, enc ? nullptr : ok_dev,
+                                     enc, lanes, st);
+    if (e != hipSuccess) return hip_fail(e, "chacha_batch hash launch");
+    if (!enc) {
+        if ((e = cipher()) != hipSuccess) return hip_fail(e, "chacha_batch cipher launch");
+        if ((e = otc_impl::chacha_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+            return hip_fail(e, "chacha_batch wipe launch");
+    }
+    return OTC_OK;
+}

@@ -54,6 +54,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 
 #include "aes.h"
@@ -237,16 +238,23 @@ __global__ __launch_bounds__(256) void k_gcm_batch_prep(const uint8_t *ivs, uint
                        b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24), 0x01000000u);
 }
 
-/* one wave per record: zero the nbytes of output of every record that failed */
+/* one wave per record: zero the nbytes of output of every record that failed.
+ * Serves both batched AEADs (otc_kernels.h batch_wipe): a descriptor is six
+ * 64-bit words with `out` in word 1 and `nbytes` in word 2 */
 constexpr uint32_t WIPE_WAVES = 4;
-__global__ __launch_bounds__(64 * WIPE_WAVES) void k_gcm_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok)
+constexpr uint32_t WIPE_WORDS = 6;
+static_assert(sizeof(otc_gcm_msg) == 8 * WIPE_WORDS && sizeof(otc_chacha_msg) == 8 * WIPE_WORDS &&
+                  offsetof(otc_gcm_msg, out) == 8 && offsetof(otc_chacha_msg, out) == 8 &&
+                  offsetof(otc_gcm_msg, nbytes) == 16 && offsetof(otc_chacha_msg, nbytes) == 16,
+              "the wipe reads the columns the two descriptors share");
+__global__ __launch_bounds__(64 * WIPE_WAVES) void k_batch_wipe(const uint64_t *msgs, uint64_t nmsg, const uint8_t *ok)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t stride = (uint64_t)gridDim.x * WIPE_WAVES;
     for (uint64_t m = (uint64_t)blockIdx.x * WIPE_WAVES + (threadIdx.x >> 6); m < nmsg; m += stride) {
         if (ok[m]) continue;
-        uint8_t *out = (uint8_t *)msgs[m].out;
-        const uint64_t n = msgs[m].nbytes, nfull = n >> 4;
+        uint8_t *out = (uint8_t *)msgs[m * WIPE_WORDS + 1];
+        const uint64_t n = msgs[m * WIPE_WORDS + 2], nfull = n >> 4;
         for (uint64_t i = lane; i < nfull; i += 64) *(uint4 *)(out + i * 16) = make_uint4(0, 0, 0, 0);
         if (lane < (n & 15u)) out[nfull * 16 + lane] = 0;
     }
@@ -325,11 +333,11 @@ hipError_t gcm_batch_prep(const uint8_t *ivs, uint64_t nmsg, otc_ctr_msg *ctr_ms
     return hipGetLastError();
 }
 
-hipError_t gcm_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+hipError_t batch_wipe(const void *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
 {
     const uint64_t want = (nmsg + WIPE_WAVES - 1) / WIPE_WAVES, cap = (uint64_t)otc_dev::device_cus() * 8;
-    hipLaunchKernelGGL(k_gcm_batch_wipe, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * WIPE_WAVES), 0, st, msgs,
-                       nmsg, ok);
+    hipLaunchKernelGGL(k_batch_wipe, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * WIPE_WAVES), 0, st,
+                       (const uint64_t *)msgs, nmsg, ok);
     return hipGetLastError();
 }
 

@@ -57,11 +57,15 @@
  * bits.  The multipliers of a Horner step are wave-uniform (SGPRs); the powers
  * of r are computed on the host, which knows r, and travel by value: no
  * setup kernel, no host synchronisation.
+ *
+ * The block function, the quad transpose and the field arithmetic live in
+ * chacha_dev.h, shared with chacha_batch.hip (many records per launch).
  */
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
+#include "chacha_dev.h"
 #include "otc_device.h"
 #include "otc_kernels.h"
 
@@ -88,64 +92,6 @@ struct CcParams {
     uint64_t nbytes; /* edge: bytes of the whole call */
 };
 
-/* rotations: 16 and 8 as byte permutes, 12 and 7 as v_alignbit_b32 */
-__device__ __forceinline__ uint32_t cc_rot16(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x01000302u); }
-__device__ __forceinline__ uint32_t cc_rot8(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x02010003u); }
-__device__ __forceinline__ uint32_t cc_rot12(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 20); }
-__device__ __forceinline__ uint32_t cc_rot7(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 25); }
-
-__device__ __forceinline__ void cc_qr(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d)
-{
-    a += b; d = cc_rot16(d ^ a);
-    c += d; b = cc_rot12(b ^ c);
-    a += b; d = cc_rot8(d ^ a);
-    c += d; b = cc_rot7(b ^ c);
-}
-
-/* the keystream block of counter `ctr` */
-__device__ __forceinline__ void cc_block(const CcParams &P, uint32_t ctr, uint32_t (&x)[16])
-{
-    const uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u,
-                            P.key[0], P.key[1], P.key[2], P.key[3], P.key[4], P.key[5], P.key[6], P.key[7],
-                            ctr, P.nonce[0], P.nonce[1], P.nonce[2]};
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] = s[i];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        cc_qr(x[0], x[4], x[8], x[12]);
-        cc_qr(x[1], x[5], x[9], x[13]);
-        cc_qr(x[2], x[6], x[10], x[14]);
-        cc_qr(x[3], x[7], x[11], x[15]);
-        cc_qr(x[0], x[5], x[10], x[15]);
-        cc_qr(x[1], x[6], x[11], x[12]);
-        cc_qr(x[2], x[7], x[8], x[13]);
-        cc_qr(x[3], x[4], x[9], x[14]);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] += s[i];
-}
-
-/* One butterfly of the 4x4 transpose among the lanes of a quad: with the
- * partner lane q ^ D, exchange quarter e | D of the lane whose bit is clear
- * with quarter e of the lane whose bit is set (hi). */
-template <int D>
-__device__ __forceinline__ void cc_xchg(uint32_t (&x)[16], bool hi)
-{
-    constexpr int ctrl = D == 1 ? 0xB1 /* quad_perm [1,0,3,2] */ : 0x4E /* [2,3,0,1] */;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if (e & D) continue;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            uint32_t &lo = x[4 * e + w], &up = x[4 * (e | D) + w];
-            const uint32_t send = hi ? lo : up;
-            const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp((int)send, (int)send, ctrl, 0xF, 0xF, false);
-            lo = hi ? recv : lo;
-            up = hi ? up : recv;
-        }
-    }
-}
-
 __global__ __launch_bounds__(64 * CC_WAVES) void k_chacha20_bulk(CcParams P)
 {
     const uint32_t lane = lane_id();
@@ -162,7 +108,7 @@ __global__ __launch_bounds__(64 * CC_WAVES) void k_chacha20_bulk(CcParams P)
         for (int j = 0; j < 4; ++j) m[j] = ld_u4<true, true>(src + j * 1024);
         uint32_t x[16];
         /* the host refuses a call whose last counter passes 2^32 - 1: no wrap */
-        cc_block(P, P.ctr0 + (uint32_t)(pass * 64) + lb, x);
+        cc_block(P.key, P.nonce, P.ctr0 + (uint32_t)(pass * 64) + lb, x);
         /* quarter j of this lane's block goes to lane 4g + j, which stores it as its piece q */
         cc_xchg<1>(x, (lane & 1u) != 0);
         cc_xchg<2>(x, (lane & 2u) != 0);
@@ -182,7 +128,7 @@ __global__ __launch_bounds__(256) void k_chacha20_edge(CcParams P)
     const uint64_t left = P.nbytes - at;
     const uint32_t m = left < 64 ? (uint32_t)left : 64u;
     uint32_t x[16];
-    cc_block(P, P.ctr0 + (uint32_t)(at / 64), x);
+    cc_block(P.key, P.nonce, P.ctr0 + (uint32_t)(at / 64), x);
     auto src = (__attribute__((address_space(1))) const uint8_t *)(P.in + at);
     auto dst = (__attribute__((address_space(1))) uint8_t *)(P.out + at);
 #pragma unroll
@@ -193,75 +139,11 @@ __global__ __launch_bounds__(256) void k_chacha20_edge(CcParams P)
 /* ======================= Poly1305 ========================================= */
 
 constexpr uint32_t PL_RUN = 32;              /* blocks per lane in a wave span */
-constexpr uint32_t PL_BATCH = 4;             /* passes per carry */
 constexpr uint32_t PL_SPAN = 64 * PL_RUN;    /* blocks of a wave span */
 constexpr uint32_t PL_WAVES = 4;             /* wave spans of a workgroup */
 constexpr int PL_MAX_LEVELS = 4;             /* 2048^4 blocks: more than any call has */
 constexpr uint32_t PL_ENTRY = 32;            /* bytes of a partial: five limbs, padded */
-constexpr uint32_t M26 = 0x3FFFFFFu;
 static_assert(PL_RUN % PL_BATCH == 0, "a wave span is whole batches");
-
-struct Fe {
-    uint32_t l[5]; /* value = sum l[i] 2^(26 i) */
-};
-struct Mul {
-    uint32_t r[5], s[4]; /* a multiplier's limbs and 5 * r[1..4] */
-};
-
-__host__ __device__ __forceinline__ Mul mul_of(const Fe &a)
-{
-    Mul m;
-    for (int i = 0; i < 5; ++i) m.r[i] = a.l[i];
-    for (int i = 0; i < 4; ++i) m.s[i] = a.l[i + 1] * 5u;
-    return m;
-}
-
-/* d += a . m, unreduced (five multiply-adds per limb) */
-__host__ __device__ __forceinline__ void fe_mac(uint64_t (&d)[5], const Fe &a, const Mul &m)
-{
-    const uint64_t a0 = a.l[0], a1 = a.l[1], a2 = a.l[2], a3 = a.l[3], a4 = a.l[4];
-    d[0] += a0 * m.r[0] + a1 * m.s[3] + a2 * m.s[2] + a3 * m.s[1] + a4 * m.s[0];
-    d[1] += a0 * m.r[1] + a1 * m.r[0] + a2 * m.s[3] + a3 * m.s[2] + a4 * m.s[1];
-    d[2] += a0 * m.r[2] + a1 * m.r[1] + a2 * m.r[0] + a3 * m.s[3] + a4 * m.s[2];
-    d[3] += a0 * m.r[3] + a1 * m.r[2] + a2 * m.r[1] + a3 * m.r[0] + a4 * m.s[3];
-    d[4] += a0 * m.r[4] + a1 * m.r[3] + a2 * m.r[2] + a3 * m.r[1] + a4 * m.r[0];
-}
-
-/* one carry chain: limbs 0, 2, 3, 4 below 2^26, limb 1 below 2^26 + 2^13 */
-__host__ __device__ __forceinline__ Fe fe_carry(uint64_t (&d)[5])
-{
-    d[1] += d[0] >> 26;
-    d[2] += d[1] >> 26;
-    d[3] += d[2] >> 26;
-    d[4] += d[3] >> 26;
-    const uint64_t t = (d[0] & M26) + (d[4] >> 26) * 5; /* 2^130 = 5 */
-    Fe f;
-    f.l[0] = (uint32_t)t & M26;
-    f.l[1] = (uint32_t)((d[1] & M26) + (t >> 26));
-    f.l[2] = (uint32_t)d[2] & M26;
-    f.l[3] = (uint32_t)d[3] & M26;
-    f.l[4] = (uint32_t)d[4] & M26;
-    return f;
-}
-
-__host__ __device__ __forceinline__ Fe fe_mul(const Fe &a, const Mul &m)
-{
-    uint64_t d[5] = {0, 0, 0, 0, 0};
-    fe_mac(d, a, m);
-    return fe_carry(d);
-}
-
-/* a 16-byte block (little-endian words) plus hibit * 2^128 */
-__host__ __device__ __forceinline__ Fe fe_of_words(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t hibit)
-{
-    Fe f;
-    f.l[0] = w0 & M26;
-    f.l[1] = (w0 >> 26 | w1 << 6) & M26;
-    f.l[2] = (w1 >> 20 | w2 << 12) & M26;
-    f.l[3] = (w2 >> 14 | w3 << 18) & M26;
-    f.l[4] = w3 >> 8 | hibit << 24;
-    return f;
-}
 
 struct PlLevel {
     const uint8_t *in;  /* level 0: the message, 16-byte aligned; above: PL_ENTRY-byte partials */
@@ -386,46 +268,11 @@ __global__ __launch_bounds__(64) void k_poly1305_final(PlFinal F)
         for (int k = 0; k < 5; ++k) h.l[k] += F.len.l[k];
         h = fe_mul(h, F.r);
     }
-    /* the full reduction: two carry chains bring h below 2^130 with every limb below 2^26 ... */
-    uint32_t h0 = h.l[0], h1 = h.l[1], h2 = h.l[2], h3 = h.l[3], h4 = h.l[4], c;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        c = h0 >> 26; h0 &= M26; h1 += c;
-        c = h1 >> 26; h1 &= M26; h2 += c;
-        c = h2 >> 26; h2 &= M26; h3 += c;
-        c = h3 >> 26; h3 &= M26; h4 += c;
-        c = h4 >> 26; h4 &= M26; h0 += c * 5;
-    }
-    c = h0 >> 26; h0 &= M26; h1 += c;
-    /* ... then g = h - p = h + 5 - 2^130, taken by a mask where it did not borrow: no branch on the value */
-    uint32_t g0 = h0 + 5;
-    c = g0 >> 26; g0 &= M26;
-    uint32_t g1 = h1 + c;
-    c = g1 >> 26; g1 &= M26;
-    uint32_t g2 = h2 + c;
-    c = g2 >> 26; g2 &= M26;
-    uint32_t g3 = h3 + c;
-    c = g3 >> 26; g3 &= M26;
-    const uint32_t g4 = h4 + c - (1u << 26);
-    const uint32_t take = (g4 >> 31) - 1u; /* all ones iff h >= p */
-    h0 = (h0 & ~take) | (g0 & take);
-    h1 = (h1 & ~take) | (g1 & take);
-    h2 = (h2 & ~take) | (g2 & take);
-    h3 = (h3 & ~take) | (g3 & take);
-    h4 = (h4 & ~take) | (g4 & take);
-    /* h mod 2^128, plus s mod 2^128 */
-    const uint32_t w0 = h0 | h1 << 26, w1 = h1 >> 6 | h2 << 20, w2 = h2 >> 12 | h3 << 14, w3 = h3 >> 18 | h4 << 8;
-    uint64_t f = (uint64_t)w0 + F.skey[0];
-    const uint32_t t0 = (uint32_t)f;
-    f = (uint64_t)w1 + F.skey[1] + (f >> 32);
-    const uint32_t t1 = (uint32_t)f;
-    f = (uint64_t)w2 + F.skey[2] + (f >> 32);
-    const uint32_t t2 = (uint32_t)f;
-    f = (uint64_t)w3 + F.skey[3] + (f >> 32);
-    const uint32_t t3 = (uint32_t)f;
+    uint32_t t[4];
+    fe_tag(h, F.skey, t);
     const uint32_t l = threadIdx.x;
     /* lanes 0..3 store one word each */
-    if (l < 4) F.out[l] = l == 0 ? t0 : l == 1 ? t1 : l == 2 ? t2 : t3;
+    if (l < 4) F.out[l] = l == 0 ? t[0] : l == 1 ? t[1] : l == 2 ? t[2] : t[3];
 }
 
 uint32_t ld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }

@@ -1,7 +1,7 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
  * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
- * stream_ops.hip), declared once: included by their callers (engine.cpp,
+ * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
  * of the public C API (otc.h).
@@ -121,8 +121,18 @@ hipError_t ghash_batch_run(const otc_gcm_msg *msgs, uint64_t nmsg, const void *t
                            const uint8_t *expect, int tag_bytes, uint8_t *ok, bool hash_out, int lanes, hipStream_t st);
 /* ivs (nmsg x 12) -> the counters of ctr_msgs (IV || 00000002) and j0 (IV || 00000001) */
 hipError_t gcm_batch_prep(const uint8_t *ivs, uint64_t nmsg, otc_ctr_msg *ctr_msgs, void *j0, hipStream_t st);
-/* zero the output of every record with ok[m] == 0 */
-hipError_t gcm_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st);
+/* zero the output of every record with ok[m] == 0.  One kernel for both batched
+ * AEADs: it reads `out` and `nbytes`, which otc_gcm_msg and otc_chacha_msg keep
+ * in the same columns of a 48-byte descriptor */
+hipError_t batch_wipe(const void *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st);
+inline hipError_t gcm_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+{
+    return batch_wipe(msgs, nmsg, ok, st);
+}
+inline hipError_t chacha_batch_wipe(const otc_chacha_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+{
+    return batch_wipe(msgs, nmsg, ok, st);
+}
 
 /* ---- aes_bs.hip ---------------------------------------------------------- */
 hipError_t bs_ctr(const void *in, void *out, size_t nbytes, const otc_aes_key &K, Ctr128 c, bool wrap64,
@@ -151,6 +161,24 @@ hipError_t poly1305_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws);
 hipError_t poly1305_run(const void *data, uint64_t nbytes, const uint32_t r[5], const uint32_t h0[5],
                         const uint8_t s[16], const uint8_t *lenblock, bool pad16, void *out16, void *ws,
                         hipStream_t st);
+
+/* ---- chacha_batch.hip ----------------------------------------------------- */
+/* lanes per record of the batched Poly1305 kernel's two forms */
+constexpr int CB_LANES_SHORT = 16, CB_LANES_LONG = 64;
+/* the batched hash kernel's boundaries in hashed blocks, smallest first */
+int chacha_batch_spans(uint64_t *spans, int max);
+/* otk[m] (32 bytes, 16-byte aligned array) = bytes 0..31 of block 0 under
+ * (keys[msgs[m].key], nonces[m]), r clamped */
+hipError_t chacha_batch_prep(const otc_chacha_msg *msgs, uint64_t nmsg, const uint8_t *keys, const uint8_t *nonces,
+                             void *otk, hipStream_t st);
+/* out = in ^ keystream from block 1 for every record, tile by tile */
+hipError_t chacha20_batch_run(const otc_chacha_msg *msgs, const uint8_t *keys, const uint8_t *nonces,
+                              const uint32_t *tile_msg, const uint64_t *tile_first, uint64_t ntiles, hipStream_t st);
+/* tags[m] = the AEAD's Poly1305 tag of record m (its `out` data with hash_out,
+ * else its `in`) under otk[m]; with ok, ok[m] = the tag equals expect[m], and
+ * the tag of a record that fails is zeroed.  lanes: CB_LANES_SHORT or _LONG */
+hipError_t poly1305_batch_run(const otc_chacha_msg *msgs, uint64_t nmsg, const void *otk, void *tags,
+                              const uint8_t *expect, uint8_t *ok, bool hash_out, int lanes, hipStream_t st);
 
 /* ---- stream_ops.hip ------------------------------------------------------ */
 hipError_t k_xor(const void *a, const void *b, void *out, size_t n, hipStream_t st);

@@ -430,6 +430,96 @@ int otc_aes_gcm_batch(const otc_gcm_msg *msgs_dev, otc_ctr_msg *ctr_msgs_dev, co
  * those (256).  Writes up to max of them; returns the count. */
 int otc_gcm_batch_spans(uint64_t *spans, int max);
 
+/* ---- batched ChaCha20-Poly1305 ----------------------------------------------
+ * Many records, each with its OWN key (an index into a key array), its own
+ * 12-byte nonce, its own AAD and its own 16-byte tag: record m is RFC 8439
+ * section 2.8 under (keys[msgs[m].key], nonces[m], aad[m]) -- ciphertext =
+ * data XOR the ChaCha20 keystream from counter 1, one-time key = bytes 0..31 of
+ * block 0, tag = Poly1305 over pad16(AAD) || pad16(ciphertext) ||
+ * le64(aad_bytes) || le64(nbytes).  The shape of WireGuard and QUIC packets,
+ * TLS 1.3 records and SSH packets, where otc_chacha20_poly1305's per-call cost
+ * (a host-side block, the host-side powers of r, an allocation, three or four
+ * launches) is all there is.  Poly1305 has no tables and its key is one-time
+ * per record by construction, so a key per record costs nothing extra: the
+ * one-time keys and the powers of r are made on the device
+ * (csrc/hip/chacha_batch.hip).
+ *
+ * Limits (the planner checks them on host copies of the descriptors): data
+ * 0 .. OTC_CHACHA_BATCH_MAX_BYTES per record, any byte count -- larger
+ * messages belong to otc_chacha20_poly1305; AAD 0 .. OTC_CHACHA_BATCH_MAX_AAD,
+ * device memory, any alignment; data buffers 16-byte aligned; in == out allowed
+ * per record; distinct records must not overlap, no input may overlap another
+ * record's output, and no AAD may overlap any record's output (an encryption
+ * writes the outputs before it hashes the AADs).  A record of 0 bytes is
+ * valid, with AAD or without.  Tags are 16 bytes.
+ *
+ * The nonces are DEVICE data supplied to every run (n x 12 bytes): a replayed
+ * batch must bring new nonces, and nonce uniqueness under a key is the
+ * caller's duty.  A run is one linear chain of launches on `stream` -- no
+ * allocation, no host synchronisation, no second stream -- so it can be
+ * captured in a graph:
+ *   encrypt: prep -> batched ChaCha20 -> batched Poly1305 over out -> tags
+ *   decrypt: prep -> batched Poly1305 over in -> tags, verdicts
+ *            -> batched ChaCha20 -> wipe
+ * prep writes every record's one-time key (r clamped, then s) into the
+ * workspace.  On decryption every computed tag is compared on the device with
+ * expect_dev (n x 16; OR of the XORs, no early exit), ok_dev[m] becomes 1 or
+ * 0, and after the cipher pass the output of every record with ok_dev[m] == 0
+ * is zeroed (in place: the ciphertext with it), and so is its row of tags_dev:
+ * the computed tag of a forged record is the valid tag of that forgery and is
+ * not handed out.  expect_dev must not overlap tags_dev or ok_dev (rejected).
+ * One kernel family: otc_last_impl does not know these calls. */
+#define OTC_CHACHA_BATCH_MAX_BYTES (1u << 20)
+#define OTC_CHACHA_BATCH_MAX_AAD (1u << 16)
+typedef struct {
+    uint64_t in;        /* device addresses */
+    uint64_t out;
+    uint64_t nbytes;
+    uint64_t aad;
+    uint64_t aad_bytes; /* the five columns of otc_gcm_msg, on purpose: the wipe kernel serves both */
+    uint64_t key;       /* index into keys_dev */
+} otc_chacha_msg;
+
+/* Host planner over HOST copies of the descriptors: checks the caps, null
+ * pointers, the alignment, key < nkeys, partial overlap of a record's in and
+ * out, overlap between records and of an AAD with any output; fills the tile
+ * map (a tile is one 4 KiB pass of one record) -- either array may be NULL to
+ * only count.  Returns the number of tiles (records of 0 bytes have none), or
+ * OTC_ERR_ARG with a message that names the record.  Needs no device. */
+int64_t otc_chacha_batch_plan(const otc_chacha_msg *msgs, size_t nmsg, size_t nkeys, uint32_t *tile_msg,
+                              uint64_t *tile_first);
+/* the caller-owned workspace of a run: the one-time keys, 32 bytes per record, 16-byte aligned */
+size_t otc_chacha_batch_ws_bytes(size_t nmsg);
+/* How many lanes hash one record: 16 (four records per wave) or 64 (one wave
+ * per record).  Both compute the same; the choice is speed only.  From HOST
+ * copies of the descriptors: 64 when the records hash more than 512 blocks
+ * (8 KiB) on average, else 16 (measured at 256 B .. 64 KiB records; what the
+ * rule rests on and what of it is supposed: aead.cpp). */
+int otc_chacha_batch_lanes(const otc_chacha_msg *msgs, size_t nmsg);
+/* The batched hash kernel's own boundaries in HASHED BLOCKS (AAD, data and
+ * length block together), smallest first: a pass of the 16-lane form (16), its
+ * batch of passes which is also a pass of the 64-lane form (64), a batch of
+ * those (256).  Writes up to max of them; returns the count. */
+int otc_chacha_batch_spans(uint64_t *spans, int max);
+/* The hash by itself: tags_dev[m] (nmsg x 16, 16-byte aligned) = Poly1305 under
+ * the one-time key otk_dev[m] (r || s, 32 bytes, r clamped here; the array
+ * 4-byte aligned) of record m's pad16(AAD) || pad16(`in` data) || lengths.
+ * lanes: 16 or 64 (0: 64). */
+int otc_poly1305_batch(const otc_chacha_msg *msgs_dev, size_t nmsg, const uint8_t *otk_dev, void *tags_dev, int lanes,
+                       void *stream);
+/* keys_dev: nkeys x 32 bytes, 4-byte aligned.  nonces_dev: nmsg x 12 bytes, any
+ * alignment.  tags_dev: nmsg x 16, 16-byte aligned, the COMPUTED tags in both
+ * directions (decryption: zero for the records that fail); expect_dev (nmsg x
+ * 16, any alignment) / ok_dev: decryption only.  ws_dev:
+ * otc_chacha_batch_ws_bytes(nmsg), 16-byte aligned.  lanes: as
+ * otc_poly1305_batch.  nmsg == 0 launches nothing; ntiles == 0 (all records
+ * empty) skips the cipher.  Every bad argument is OTC_ERR_ARG before any HIP
+ * call. */
+int otc_chacha20_poly1305_batch(const otc_chacha_msg *msgs_dev, const uint32_t *tile_msg_dev,
+                                const uint64_t *tile_first_dev, uint64_t ntiles, size_t nmsg, const uint8_t *keys_dev,
+                                int dir, const uint8_t *nonces_dev, void *tags_dev, const uint8_t *expect_dev,
+                                uint8_t *ok_dev, void *ws_dev, int lanes, void *stream);
+
 /* out = a ^ b (the device arc4_crypt combiner). */
 int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream);
 

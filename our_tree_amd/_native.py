@@ -243,6 +243,13 @@ def _declare_gpu(lib):
         "otc_poly1305": (c_int, [c_vp, c_sz, c_u8p, c_vp, c_vp]),
         "otc_poly1305_spans": (c_int, [P(c_u64), c_int]),
         "otc_chacha20_poly1305": (c_int, [c_vp, c_vp, c_sz, c_u8p, c_int, c_u8p, c_u8p, c_sz, c_vp, c_vp]),
+        "otc_chacha_batch_plan": (ctypes.c_int64, [c_vp, c_sz, c_sz, c_vp, c_vp]),
+        "otc_chacha_batch_ws_bytes": (c_sz, [c_sz]),
+        "otc_chacha_batch_lanes": (c_int, [c_vp, c_sz]),
+        "otc_chacha_batch_spans": (c_int, [P(c_u64), c_int]),
+        "otc_poly1305_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
+        "otc_chacha20_poly1305_batch": (c_int, [c_vp, c_vp, c_vp, c_u64, c_sz, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
+                                                c_vp, c_int, c_vp]),
         "otc_split_stats": (None, [c_int]),
         "otc_split_fallback_reason": (ctypes.c_char_p, []),
         "otc_split_last_units": (c_int, [ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64)]),

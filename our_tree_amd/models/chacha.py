@@ -14,7 +14,8 @@ class ChaCha20Poly1305:
     place allowed), ``bytes`` to the C oracle.  ``encrypt`` returns
     ``(ciphertext, tag)``; ``decrypt`` takes the received 16-byte tag and
     raises ``ops.ChaChaTagError`` -- with the output zeroed -- when it does
-    not match."""
+    not match.  ``encrypt_batch`` / ``decrypt_batch`` take many GPU records at
+    once, all under this key (``ops.chacha_batch_ops.ChaChaBatch``)."""
 
     def __init__(self, key: bytes):
         key = bytes(key)
@@ -31,3 +32,15 @@ class ChaCha20Poly1305:
         if isinstance(data, torch.Tensor):
             return ops.chacha20_poly1305_decrypt(data, self._key, nonce, tag, aad, out=out)
         return cpu_ref.chacha20_poly1305_auth_decrypt(self._key, nonce, data, tag, aad)
+
+    def encrypt_batch(self, xs, nonces: torch.Tensor, aads=None, outs=None):
+        """Many GPU records under this key, record m with ``nonces[m]`` (a
+        device uint8 [n, 12] tensor) and ``aads[m]``: ``(outs, tags)`` with the
+        tags a device uint8 [n, 16] tensor."""
+        return ops.chacha_batch_ops.chacha20_poly1305_encrypt_batch(xs, self._key, nonces, aads=aads, outs=outs)
+
+    def decrypt_batch(self, xs, nonces: torch.Tensor, tags: torch.Tensor, aads=None, outs=None):
+        """``(outs, ok)``: ``ok`` is a device bool [n] tensor; the output of
+        every record whose tag does not match is zeroed.  Nothing is read
+        back and nothing is raised: check ``ok``."""
+        return ops.chacha_batch_ops.chacha20_poly1305_decrypt_batch(xs, self._key, nonces, tags, aads=aads, outs=outs)

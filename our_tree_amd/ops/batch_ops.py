@@ -1,8 +1,8 @@
 """Planned batches of small messages: ``CtrBatch`` (AES-CTR, own key and
 counter each, ``csrc/hip/aes_tt.hip``) and ``GcmBatch`` (AES-GCM records under
 one key, ``csrc/hip/aes_gcm_batch.hip``), and the planning pieces they share:
-the packed-buffer layout, the per-tensor descriptors, the key index and the
-plan's pinned upload."""
+the packed-buffer layout, the per-tensor descriptors, the key index, the AAD
+columns and the plan's pinned upload (``chacha_batch_ops`` uses them too)."""
 from __future__ import annotations
 
 import ctypes
@@ -137,6 +137,59 @@ def _tensor_descs(xs, outs, device, noun: str):
         if _nbytes(o) != nb:
             raise ValueError(f"outs[{i}] must have the byte size of xs[{i}]")
         yield i, x.data_ptr(), o.data_ptr(), nb
+
+
+def _set_aads(desc, aads, device, keep):
+    """Columns 3 and 4 of a batched AEAD's descriptors (``GcmBatch`` and
+    ``chacha_batch_ops.ChaChaBatch``, whose AAD cap is the same); host AADs go
+    to one device buffer.  ``keep`` collects what must stay alive."""
+    import numpy as np
+    n = desc.shape[0]
+    if aads is None or n == 0:
+        if isinstance(aads, (list, tuple)) and len(aads) != n:
+            raise ValueError("one AAD per record")
+        return
+    if isinstance(aads, torch.Tensor):
+        _check_dev(aads, "aads")
+        if aads.dtype != torch.uint8 or aads.dim() != 2 or aads.shape[0] != n:
+            raise ValueError(f"aads must be a uint8 [{n}, A] tensor")
+        if aads.device != device:
+            raise ValueError("aads must be on the records' device")
+        a = int(aads.shape[1])
+        if a > GCM_BATCH_MAX_AAD:
+            raise ValueError("a record has at most 64 KiB of AAD")
+        keep.append(aads)
+        if a:
+            desc[:, 3] = np.uint64(aads.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(a)
+            desc[:, 4] = a
+        return
+    aads = list(aads)
+    if len(aads) != n:
+        raise ValueError("one AAD per record")
+    host, blob = [], _Blob()
+    for i, a in enumerate(aads):
+        if isinstance(a, torch.Tensor):
+            _check_dev(a, f"aads[{i}]")
+            if a.device != device:
+                raise ValueError("aads must be on the records' device")
+            na = _nbytes(a)
+            addr = a.data_ptr()
+        else:
+            a = b"" if a is None else bytes(a)
+            na, addr = len(a), None
+        if na > GCM_BATCH_MAX_AAD:
+            raise ValueError(f"record {i}: more than 64 KiB of AAD")
+        if na and addr is None:
+            host.append((i, blob.add(a, 1)))  # back to back: an AAD takes any alignment
+        elif na:
+            desc[i, 3] = addr
+        desc[i, 4] = na
+    keep.append(aads)
+    if host:
+        dev = blob.upload(device)
+        keep.append(dev)
+        for i, off in host:
+            desc[i, 3] = dev.data_ptr() + off
 
 
 class CtrBatch:
@@ -398,54 +451,7 @@ class GcmBatch:
         self.tags = self.ok = None
 
     def _set_aads(self, desc, aads):
-        """Columns 3 and 4 of the descriptors; host AADs go to one device buffer."""
-        import numpy as np
-        n = desc.shape[0]
-        if aads is None or n == 0:
-            if isinstance(aads, (list, tuple)) and len(aads) != n:
-                raise ValueError("one AAD per record")
-            return
-        if isinstance(aads, torch.Tensor):
-            _check_dev(aads, "aads")
-            if aads.dtype != torch.uint8 or aads.dim() != 2 or aads.shape[0] != n:
-                raise ValueError(f"aads must be a uint8 [{n}, A] tensor")
-            if aads.device != self.device:
-                raise ValueError("aads must be on the records' device")
-            a = int(aads.shape[1])
-            if a > GCM_BATCH_MAX_AAD:
-                raise ValueError("a record has at most 64 KiB of AAD")
-            self._keep.append(aads)
-            if a:
-                desc[:, 3] = np.uint64(aads.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(a)
-                desc[:, 4] = a
-            return
-        aads = list(aads)
-        if len(aads) != n:
-            raise ValueError("one AAD per record")
-        host, blob = [], _Blob()
-        for i, a in enumerate(aads):
-            if isinstance(a, torch.Tensor):
-                _check_dev(a, f"aads[{i}]")
-                if a.device != self.device:
-                    raise ValueError("aads must be on the records' device")
-                na = _nbytes(a)
-                addr = a.data_ptr()
-            else:
-                a = b"" if a is None else bytes(a)
-                na, addr = len(a), None
-            if na > GCM_BATCH_MAX_AAD:
-                raise ValueError(f"record {i}: more than 64 KiB of AAD")
-            if na and addr is None:
-                host.append((i, blob.add(a, 1)))  # back to back: an AAD takes any alignment
-            elif na:
-                desc[i, 3] = addr
-            desc[i, 4] = na
-        self._keep.append(aads)
-        if host:
-            dev = blob.upload(self.device)
-            self._keep.append(dev)
-            for i, off in host:
-                desc[i, 3] = dev.data_ptr() + off
+        _set_aads(desc, aads, self.device, self._keep)
 
     def _build(self, desc, tile_blocks):
         """Planner (validation + the CTR half's tile map) -> one pinned upload;
