@@ -767,6 +767,226 @@ int aes_gcm_auth_decrypt(aes_gcm_context *ctx, size_t length, const unsigned cha
 }
 
 /* ---------------------------------------------------------------------------
+ * AES-OCB3 (RFC 7253), written from the RFC.  Strings are big-endian 128-bit
+ * blocks: double() shifts the 16 bytes left by one bit and folds a bit shifted
+ * out of byte 0 back as 0x87 into byte 15.
+ * ------------------------------------------------------------------------- */
+static void ocb_double(unsigned char out[16], const unsigned char in[16])
+{
+    const unsigned carry = in[0] >> 7;
+    for (int i = 0; i < 15; ++i) out[i] = (unsigned char)((in[i] << 1) | (in[i + 1] >> 7));
+    out[15] = (unsigned char)((in[15] << 1) ^ (carry ? 0x87 : 0));
+}
+
+static inline void xor16(unsigned char *d, const unsigned char *a, const unsigned char *b)
+{
+    for (int i = 0; i < 16; ++i) d[i] = (unsigned char)(a[i] ^ b[i]);
+}
+
+/* L_*, L_$ and L_0..L_32 from the encryption schedule already in ctx->enc */
+static void ocb_set_l(aes_ocb_context *ctx)
+{
+    const unsigned char zero[16] = {0};
+    ensure_tables();
+    encrypt_block(&ctx->enc, zero, ctx->l_star);
+    ocb_double(ctx->l_dollar, ctx->l_star);
+    ocb_double(ctx->l[0], ctx->l_dollar);
+    for (int j = 1; j <= 32; ++j) ocb_double(ctx->l[j], ctx->l[j - 1]);
+}
+
+int aes_ocb_setkey(aes_ocb_context *ctx, const unsigned char *key, unsigned int keybits)
+{
+    int r = aes_setkey_enc(&ctx->enc, key, keybits);
+    if (r == 0) r = aes_setkey_dec(&ctx->dec, key, keybits);
+    if (r) return r;
+    ocb_set_l(ctx);
+    return 0;
+}
+
+int aes_ocb_offset0(const aes_ocb_context *ctx, const unsigned char *nonce, size_t nonce_len, size_t tag_len,
+                    unsigned char out[16])
+{
+    if (!nonce || nonce_len < 1 || nonce_len > 15 || tag_len < 1 || tag_len > 16)
+        return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    /* Nonce = num2str(TAGLEN mod 128, 7) || 0* || 1 || N */
+    unsigned char nb[16] = {0}, stretch[24];
+    nb[0] = (unsigned char)(((8 * tag_len) % 128) << 1);
+    nb[15 - nonce_len] |= 1;
+    memcpy(nb + 16 - nonce_len, nonce, nonce_len);
+    const unsigned bottom = nb[15] & 63u;
+    nb[15] &= 0xC0;
+    ensure_tables();
+    encrypt_block(&ctx->enc, nb, stretch); /* Ktop */
+    for (int i = 0; i < 8; ++i) stretch[16 + i] = (unsigned char)(stretch[i] ^ stretch[i + 1]);
+    const unsigned bs = bottom / 8, bb = bottom % 8;
+    for (int i = 0; i < 16; ++i)
+        out[i] = (unsigned char)((stretch[i + bs] << bb) | (bb ? stretch[i + bs + 1] >> (8 - bb) : 0));
+    return 0;
+}
+
+void aes_ocb_offset(const aes_ocb_context *ctx, const unsigned char offset0[16], uint64_t i, unsigned char out[16])
+{
+    unsigned char o[16];
+    memcpy(o, offset0, 16);
+    const uint64_t g = i ^ (i >> 1);
+    for (int j = 0; j <= 32; ++j)
+        if ((g >> j) & 1u) xor16(o, o, ctx->l[j]);
+    memcpy(out, o, 16);
+}
+
+static inline int ocb_ntz(uint64_t i) { return __builtin_ctzll(i); }
+
+void aes_ocb_hash(const aes_ocb_context *ctx, const unsigned char *aad, size_t len, unsigned char out[16])
+{
+    unsigned char off[16] = {0}, sum[16] = {0}, t[16];
+    ensure_tables();
+    uint64_t i = 0;
+    for (; len >= 16; aad += 16, len -= 16) {
+        ++i;
+        xor16(off, off, ctx->l[ocb_ntz(i)]);
+        xor16(t, aad, off);
+        encrypt_block(&ctx->enc, t, t);
+        xor16(sum, sum, t);
+    }
+    if (len) {
+        xor16(off, off, ctx->l_star);
+        memset(t, 0, 16);
+        memcpy(t, aad, len);
+        t[len] = 0x80;
+        xor16(t, t, off);
+        encrypt_block(&ctx->enc, t, t);
+        xor16(sum, sum, t);
+    }
+    memcpy(out, sum, 16);
+}
+
+static void ocb_blocks_serial(const aes_ocb_context *ctx, int mode, const unsigned char offset0[16], uint64_t first,
+                              uint64_t nblocks, const unsigned char *in, unsigned char *out, unsigned char cs[16])
+{
+    unsigned char off[16], t[16];
+    aes_ocb_offset(ctx, offset0, first, off);
+    for (uint64_t k = 0; k < nblocks; ++k, in += 16, out += 16) {
+        xor16(off, off, ctx->l[ocb_ntz(first + k + 1)]);
+        if (mode == AES_ENCRYPT) {
+            xor16(cs, cs, in);
+            xor16(t, in, off);
+            encrypt_block(&ctx->enc, t, t);
+            xor16(out, t, off);
+        } else {
+            xor16(t, in, off);
+            decrypt_block(&ctx->dec, t, t);
+            xor16(out, t, off);
+            xor16(cs, cs, out);
+        }
+    }
+}
+
+typedef struct {
+    const aes_ocb_context *ctx;
+    int mode;
+    const unsigned char *offset0;
+    uint64_t first, nblocks;
+    const unsigned char *in;
+    unsigned char *out;
+    unsigned char cs[16];
+} ocb_job;
+
+static void *ocb_worker(void *arg)
+{
+    ocb_job *j = (ocb_job *)arg;
+    ocb_blocks_serial(j->ctx, j->mode, j->offset0, j->first, j->nblocks, j->in, j->out, j->cs);
+    return NULL;
+}
+
+/* Large calls (the device tests' oracle) run T pieces on T threads, each from
+ * the closed-form offset of its first block, and XOR the pieces' checksums. */
+int aes_crypt_ocb_blocks(const aes_ocb_context *ctx, int mode, const unsigned char offset0[16], uint64_t first_block,
+                         uint64_t nblocks, const unsigned char *input, unsigned char *output,
+                         unsigned char checksum[16])
+{
+    enum { MAXT = 8 };
+    if (first_block > AES_OCB_MAX_BLOCKS || nblocks > AES_OCB_MAX_BLOCKS - first_block)
+        return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    ensure_tables();
+    if (nblocks < ((uint64_t)1 << 16)) {
+        ocb_blocks_serial(ctx, mode, offset0, first_block, nblocks, input, output, checksum);
+        return 0;
+    }
+    ocb_job jobs[MAXT];
+    pthread_t th[MAXT];
+    const uint64_t per = nblocks / MAXT;
+    for (uint64_t t = 0; t < MAXT; ++t) {
+        jobs[t].ctx = ctx;
+        jobs[t].mode = mode;
+        jobs[t].offset0 = offset0;
+        jobs[t].first = first_block + t * per;
+        jobs[t].nblocks = t + 1 == MAXT ? nblocks - t * per : per;
+        jobs[t].in = input + 16 * t * per;
+        jobs[t].out = output + 16 * t * per;
+        memset(jobs[t].cs, 0, 16);
+    }
+    for (size_t t = 1; t < MAXT; ++t) pthread_create(&th[t], NULL, ocb_worker, &jobs[t]);
+    ocb_worker(&jobs[0]);
+    for (size_t t = 1; t < MAXT; ++t) pthread_join(th[t], NULL);
+    for (size_t t = 0; t < MAXT; ++t) xor16(checksum, checksum, jobs[t].cs);
+    return 0;
+}
+
+int aes_crypt_ocb(const aes_ocb_context *ctx, int mode, size_t length, const unsigned char *nonce, size_t nonce_len,
+                  const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                  unsigned char tag[16], size_t tag_len)
+{
+    unsigned char off[16], off0[16], cs[16] = {0}, t[16];
+    if ((uint64_t)length > AES_OCB_MAX_BYTES) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    if (aes_ocb_offset0(ctx, nonce, nonce_len, tag_len, off0)) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    /* this copy's tables: in a process that holds two copies of this file the
+     * calls above and below may run in the other one (see aes_gcm_setkey) */
+    ensure_tables();
+    const uint64_t m = (uint64_t)length / 16;
+    const size_t r = length % 16;
+    aes_crypt_ocb_blocks(ctx, mode, off0, 0, m, input, output, cs);
+    aes_ocb_offset(ctx, off0, m, off);
+    if (r) {
+        unsigned char pad[16], p[16] = {0};
+        const unsigned char *in = input + 16 * m;
+        unsigned char *out = output + 16 * m;
+        xor16(off, off, ctx->l_star);
+        encrypt_block(&ctx->enc, off, pad);
+        for (size_t i = 0; i < r; ++i) {
+            const unsigned char c = (unsigned char)(in[i] ^ pad[i]);
+            p[i] = mode == AES_ENCRYPT ? in[i] : c; /* the plaintext, either way */
+            out[i] = c;
+        }
+        p[r] = 0x80;
+        xor16(cs, cs, p);
+    }
+    xor16(t, cs, off);
+    xor16(t, t, ctx->l_dollar);
+    encrypt_block(&ctx->enc, t, t);
+    aes_ocb_hash(ctx, aad, aad_len, off);
+    xor16(t, t, off);
+    memset(tag, 0, 16);
+    memcpy(tag, t, tag_len);
+    return 0;
+}
+
+int aes_ocb_auth_decrypt(const aes_ocb_context *ctx, size_t length, const unsigned char *nonce, size_t nonce_len,
+                         const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
+                         const unsigned char *input, unsigned char *output)
+{
+    unsigned char t[16];
+    const int r = aes_crypt_ocb(ctx, AES_DECRYPT, length, nonce, nonce_len, aad, aad_len, input, output, t, tag_len);
+    if (r) return r;
+    unsigned diff = 0; /* every byte compared, whatever the earlier ones gave */
+    for (size_t i = 0; i < tag_len; ++i) diff |= (unsigned)(t[i] ^ tag[i]);
+    if (diff) {
+        if (length) memset(output, 0, length);
+        return POLARSSL_ERR_OCB_AUTH_FAILED;
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------
  * Self test: FIPS-197 appendix C, SP 800-38A F.1/F.2/F.3/F.5, RFC 3686 #1-#3,
  * and the 10,000-iteration Monte-Carlo ECB/CBC chains of the NIST
  * rijndael-vals set that the reference's self-test runs

@@ -1,6 +1,7 @@
 /*
  * aead.cpp -- the hash and authenticated-encryption ops of the C API (otc.h):
  * GHASH and AES-GCM (counter mode: engine.cpp's ctr32_run; hash: aes_gcm.hip),
+ * AES-OCB3 (aes_ocb.hip),
  * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), batched GCM
  * (aes_gcm_batch.hip and the batched CTR kernel) and batched
  * ChaCha20-Poly1305 (chacha_batch.hip): the argument checks, what an
@@ -109,6 +110,99 @@ extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_g
     e = otc_impl::ghash_run(dir == OTC_DIR_ENCRYPT ? out : in, nbytes, k->h, y0, lenblock, ekj0, tag_dev, ws, st);
     if (e != hipSuccess) return hip_fail(e, "gcm hash launch");
     if (dir == OTC_DIR_DECRYPT && nbytes) return ctr32_run(in, out, nbytes, &k->enc, ctr, impl, stream);
+    return OTC_OK;
+}
+
+/* ---- AES-OCB3 (RFC 7253) ---------------------------------------------------- */
+extern "C" int otc_ocb_spans(uint64_t *spans, int max) { return otc_impl::ocb_spans(spans, spans ? max : 0); }
+
+extern "C" int otc_ocb_key_init(otc_ocb_key *k, const uint8_t *key, int keybits)
+{
+    if (!k || !key) return set_err(OTC_ERR_ARG, "null argument");
+    aes_ocb_context c;
+    if (aes_ocb_setkey(&c, key, (unsigned)keybits)) return set_err(OTC_ERR_ARG, "invalid AES key size (must be 128/192/256)");
+    if (int r = otc_aes_key_init(&k->enc, key, keybits, OTC_DIR_ENCRYPT)) return r;
+    if (int r = otc_aes_key_init(&k->dec, key, keybits, OTC_DIR_DECRYPT)) return r;
+    memcpy(k->l_star, c.l_star, 16);
+    memcpy(k->l_dollar, c.l_dollar, 16);
+    memcpy(k->l, c.l, sizeof k->l);
+    return OTC_OK;
+}
+
+/* what both OCB calls check of the key and the direction */
+static int ocb_check_key(const otc_ocb_key *k, int dir)
+{
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->enc, OTC_DIR_ENCRYPT)) return r;
+    if (int r = check_key(&k->dec, OTC_DIR_DECRYPT)) return r;
+    if (k->enc.nr != k->dec.nr) return set_err(OTC_ERR_ARG, "ocb: the two schedules are of different keys");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    return OTC_OK;
+}
+
+/* the host oracle's context over the key's encryption schedule and L table:
+ * the offsets and the AAD's hash never run the inverse cipher, so c.dec stays unset */
+static void ocb_host_ctx(aes_ocb_context &c, const otc_ocb_key *k)
+{
+    aes_import_rk32(&c.enc, k->enc.rk, k->enc.nr);
+    memcpy(c.l_star, k->l_star, 16);
+    memcpy(c.l_dollar, k->l_dollar, 16);
+    memcpy(c.l, k->l, sizeof c.l);
+}
+
+extern "C" int otc_aes_ocb_blocks(const void *in, void *out, uint64_t nblocks, const otc_ocb_key *k, int dir,
+                                  const uint8_t offset0[16], uint64_t first_block, void *checksum_dev, void *stream)
+{
+    Range rg("otc_aes_ocb_blocks");
+    if (int r = ocb_check_key(k, dir)) return r;
+    if (!offset0) return set_err(OTC_ERR_ARG, "ocb_blocks: null offset");
+    if (!checksum_dev || ((uintptr_t)checksum_dev & 15u))
+        return set_err(OTC_ERR_ARG, "ocb_blocks: the checksum must be 16-byte aligned device memory");
+    if (first_block > AES_OCB_MAX_BLOCKS || nblocks > AES_OCB_MAX_BLOCKS - first_block)
+        return set_err(OTC_ERR_ARG, "ocb_blocks: block indices would pass 2^32");
+    if (int r = check_bufs(in, out, (size_t)nblocks * 16, true, "aes_ocb_blocks")) return r;
+    set_last_impl(OTC_IMPL_TTABLE);
+    const hipError_t e = otc_impl::ocb_bulk(in, out, first_block, nblocks, dir == OTC_DIR_ENCRYPT ? k->enc : k->dec,
+                                            offset0, k->l, checksum_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "aes_ocb_blocks launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_ocb(const void *in, void *out, size_t nbytes, const otc_ocb_key *k, int dir, const uint8_t *nonce,
+                           size_t nonce_len, const uint8_t *aad, size_t aad_len, int tag_bytes, void *tag_dev,
+                           void *stream)
+{
+    Range rg("otc_aes_ocb");
+    if (int r = ocb_check_key(k, dir)) return r;
+    if (!nonce || nonce_len < 1 || nonce_len > 15) return set_err(OTC_ERR_ARG, "ocb: the nonce has 1 to 15 bytes");
+    if (tag_bytes < 1 || tag_bytes > 16) return set_err(OTC_ERR_ARG, "ocb: a tag has 1 to 16 bytes");
+    if (aad_len && !aad) return set_err(OTC_ERR_ARG, "ocb: null aad");
+    if (!tag_dev || ((uintptr_t)tag_dev & 3u)) return set_err(OTC_ERR_ARG, "ocb: the tag must be 4-byte aligned device memory");
+    if ((uint64_t)nbytes > OTC_OCB_MAX_BYTES) return set_err(OTC_ERR_ARG, "ocb: a message has at most 2^36 bytes");
+    if (int r = check_bufs(in, out, nbytes, true, "aes_ocb")) return r;
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+
+    /* what does not depend on the data, on the host */
+    aes_ocb_context c;
+    ocb_host_ctx(c, k);
+    const uint64_t m = (uint64_t)nbytes / 16;
+    const uint32_t r = (uint32_t)(nbytes % 16);
+    uint8_t off0[16], off_m[16], hash[16];
+    aes_ocb_offset0(&c, nonce, nonce_len, (size_t)tag_bytes, off0);
+    aes_ocb_offset(&c, off0, m, off_m);
+    aes_ocb_hash(&c, aad, aad_len, hash);
+
+    /* the tag's 16 bytes collect the whole blocks' checksum; the finisher reads it and writes the tag over it */
+    hipError_t e = hipSuccess;
+    if (m) {
+        if ((e = otc_impl::ocb_clear(tag_dev, st)) != hipSuccess) return hip_fail(e, "aes_ocb checksum clear");
+        e = otc_impl::ocb_bulk(in, out, 0, m, dir == OTC_DIR_ENCRYPT ? k->enc : k->dec, off0, k->l, tag_dev, st);
+        if (e != hipSuccess) return hip_fail(e, "aes_ocb launch");
+    }
+    e = otc_impl::ocb_finish((const uint8_t *)in + 16 * m, (uint8_t *)out + 16 * m, r, dir == OTC_DIR_DECRYPT, k->enc,
+                             off_m, k->l_star, k->l_dollar, hash, tag_bytes, m ? tag_dev : nullptr, tag_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "aes_ocb finisher launch");
     return OTC_OK;
 }
 

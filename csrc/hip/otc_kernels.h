@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
+ * aes_xts.hip, aes_ocb.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
  * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
@@ -91,6 +91,26 @@ hipError_t xts_bulk(const void *in, void *out, uint64_t nblocks, uint32_t unit_b
  * (queued behind xts_bulk over its first m - 1 blocks) */
 hipError_t xts_steal(const void *in, void *out, uint32_t m, uint32_t r, const otc_aes_key &K1, const otc_aes_key &K2,
                      const uint8_t tweak0[16], hipStream_t st);
+
+/* ---- aes_ocb.hip --------------------------------------------------------- */
+/* the bulk kernel's boundaries in bytes, smallest first; returns how many there are */
+int ocb_spans(uint64_t *spans, int max);
+/* zero the 16 bytes of a checksum accumulator (4-byte aligned), in stream order */
+hipError_t ocb_clear(void *checksum, hipStream_t st);
+/* OCB3 over the whole blocks first_block + 1 .. first_block + nblocks of the
+ * message whose Offset_0 is given (first_block + nblocks <= 2^32); in and out
+ * address the first of them.  K: the key in the call's direction, l: L_0 ..
+ * L_32.  The XOR of the blocks' plaintexts is XORed into the 16 device bytes
+ * at checksum (4-byte aligned). */
+hipError_t ocb_bulk(const void *in, void *out, uint64_t first_block, uint64_t nblocks, const otc_aes_key &K,
+                    const uint8_t offset0[16], const uint8_t (*l)[16], void *checksum, hipStream_t st);
+/* the trailing r < 16 bytes at in / out (offset_m: Offset of the last whole
+ * block) and the tag: tag[0 .. tag_bytes) = the tag, the rest of its 16 bytes
+ * zero.  checksum: the whole blocks' (it may be the tag's own 16 bytes), or
+ * null for none.  Kenc: the encryption schedule, in both directions. */
+hipError_t ocb_finish(const void *in, void *out, uint32_t r, bool dec, const otc_aes_key &Kenc,
+                      const uint8_t offset_m[16], const uint8_t l_star[16], const uint8_t l_dollar[16],
+                      const uint8_t hash[16], int tag_bytes, const void *checksum, void *tag, hipStream_t st);
 
 /* ---- aes_gcm.hip --------------------------------------------------------- */
 /* byte sizes of the GHASH decomposition's pieces, smallest first; returns how many there are */

@@ -128,6 +128,47 @@ int aes_gcm_auth_decrypt(aes_gcm_context *ctx, size_t length, const unsigned cha
                          const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
                          const unsigned char *input, unsigned char *output);
 
+/* AES-OCB3 (RFC 7253), written from the RFC (the reference has no
+ * authenticated mode): one block-cipher call per block, the tag from an XOR of
+ * the plaintext blocks.  Offset_i = Offset_0 ^ XOR{ L_j : bit j of i ^ (i >> 1) },
+ * so every block is independent; a message has at most 2^36 bytes, block
+ * indices reach 2^32 and the table L_0 .. L_32.  Tag lengths are in BYTES
+ * (1..16) and enter the nonce block: another length, another ciphertext. */
+#define POLARSSL_ERR_OCB_AUTH_FAILED -0x0014
+#define AES_OCB_MAX_BYTES (((uint64_t)1) << 36)
+#define AES_OCB_MAX_BLOCKS (((uint64_t)1) << 32)
+typedef struct {
+    aes_context enc;             /* K, encryption schedule */
+    aes_context dec;             /* K, decryption schedule */
+    unsigned char l_star[16];    /* L_* = E_K(0^128) */
+    unsigned char l_dollar[16];  /* L_$ = double(L_*) */
+    unsigned char l[33][16];     /* L_0 = double(L_$), L_j = double(L_{j-1}) */
+} aes_ocb_context;
+int aes_ocb_setkey(aes_ocb_context *ctx, const unsigned char *key, unsigned int keybits);
+/* Offset_0 of (nonce, tag length): nonce_len 1..15, tag_len 1..16 bytes */
+int aes_ocb_offset0(const aes_ocb_context *ctx, const unsigned char *nonce, size_t nonce_len, size_t tag_len,
+                    unsigned char out[16]);
+/* Offset_i by the closed form, 0 <= i <= 2^32 */
+void aes_ocb_offset(const aes_ocb_context *ctx, const unsigned char offset0[16], uint64_t i, unsigned char out[16]);
+/* HASH(K, A); an empty A hashes to 0 */
+void aes_ocb_hash(const aes_ocb_context *ctx, const unsigned char *aad, size_t len, unsigned char out[16]);
+/* blocks first_block + 1 .. first_block + nblocks of the message whose
+ * Offset_0 is given; the XOR of their plaintexts is XORed into checksum.
+ * first_block + nblocks <= 2^32.  May run in place. */
+int aes_crypt_ocb_blocks(const aes_ocb_context *ctx, int mode, const unsigned char offset0[16], uint64_t first_block,
+                         uint64_t nblocks, const unsigned char *input, unsigned char *output,
+                         unsigned char checksum[16]);
+/* mode AES_ENCRYPT / AES_DECRYPT; tag: the COMPUTED tag in both directions,
+ * its first tag_len bytes, the rest of the 16 zero.  May run in place. */
+int aes_crypt_ocb(const aes_ocb_context *ctx, int mode, size_t length, const unsigned char *nonce, size_t nonce_len,
+                  const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                  unsigned char tag[16], size_t tag_len);
+/* decrypts and compares the tag_len (1..16) tag bytes in constant time; on a
+ * mismatch output is zeroed and POLARSSL_ERR_OCB_AUTH_FAILED returned */
+int aes_ocb_auth_decrypt(const aes_ocb_context *ctx, size_t length, const unsigned char *nonce, size_t nonce_len,
+                         const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
+                         const unsigned char *input, unsigned char *output);
+
 /* Monte-Carlo known-answer chains of the reference self-test
  * (aes-modes/aes.c:1084-1200): 10,000 chained operations from an all-zero
  * key / block / IV.  aes_monte_carlo writes the final block (CBC-enc: the last

@@ -252,6 +252,50 @@ int otc_ghash(const void *data, size_t nbytes, const uint8_t h[16], const uint8_
  * kernel takes another path.  Writes up to max of them; returns the count. */
 int otc_ghash_spans(uint64_t *spans, int max);
 
+/* AES-OCB3 (RFC 7253) of ONE message in device memory, 128/192/256-bit keys:
+ * an AEAD in one pass -- one block-cipher call per block, the tag from an XOR
+ * of the plaintext blocks (csrc/hip/aes_ocb.hip).  nbytes is 0 .. 2^36 (any
+ * byte count), the nonce 1..15 bytes, tag_bytes 1..16; the tag length enters
+ * the nonce block, so another tag length gives another ciphertext.  nonce and
+ * aad are HOST memory, as in otc_aes_gcm.  dir is OTC_DIR_ENCRYPT or
+ * OTC_DIR_DECRYPT; tag_dev is 16 bytes of 4-byte aligned device memory that
+ * receive the COMPUTED tag in both directions: its first tag_bytes are the
+ * tag, the rest zero (comparing it with a received tag is the caller's:
+ * ops.ocb_decrypt does it with one readback).  Offset_0, HASH(K, A) and the
+ * last whole block's offset are computed on the host and travel by value: the
+ * call does not synchronise, allocates nothing and can be captured in a
+ * graph.  Stream order: tag_dev is cleared and collects the whole blocks'
+ * checksum from the bulk kernel; a one-lane finisher handles the trailing
+ * bytes and turns the checksum into the tag.  Fewer than 16 bytes launch only
+ * the finisher.  Buffers are 16-byte aligned; in place is allowed both ways.
+ * Every bad argument is OTC_ERR_ARG before any HIP call.  otc_last_impl:
+ * OTC_IMPL_TTABLE (there is one kernel family and no impl argument). */
+#define OTC_OCB_MAX_BYTES (((uint64_t)1) << 36)
+typedef struct {
+    otc_aes_key enc;      /* K's encryption schedule */
+    otc_aes_key dec;      /* K's decryption schedule (equivalent inverse) */
+    uint8_t l_star[16];   /* L_* = E_K(0^128) */
+    uint8_t l_dollar[16]; /* L_$ = double(L_*) */
+    uint8_t l[33][16];    /* L_0 = double(L_$), L_j = double(L_{j-1}) */
+} otc_ocb_key;
+int otc_ocb_key_init(otc_ocb_key *k, const uint8_t *key, int keybits);
+int otc_aes_ocb(const void *in, void *out, size_t nbytes, const otc_ocb_key *k, int dir, const uint8_t *nonce,
+                size_t nonce_len, const uint8_t *aad, size_t aad_len, int tag_bytes, void *tag_dev, void *stream);
+/* The primitive: the whole blocks first_block + 1 .. first_block + nblocks of
+ * a message whose Offset_0 (host memory, 16 bytes) is given, in and out
+ * addressing the first of them; first_block + nblocks <= 2^32.  The XOR of
+ * those blocks' plaintexts is XORed into the 16 device bytes at checksum_dev
+ * (16-byte aligned; the caller zeroes them before the first piece).  A
+ * message can be cut across calls, streams or devices this way; the caller
+ * finishes it (the trailing bytes and the tag: aes.h aes_crypt_ocb shows how). */
+int otc_aes_ocb_blocks(const void *in, void *out, uint64_t nblocks, const otc_ocb_key *k, int dir,
+                       const uint8_t offset0[16], uint64_t first_block, void *checksum_dev, void *stream);
+/* Byte sizes at which the bulk kernel takes another path, smallest first (a
+ * lane's block, one load of a wave, a pass, a wave's run, a workgroup's chunk,
+ * and the full grid's first step -- past it workgroups take a second grid
+ * step), like otc_ghash_spans. */
+int otc_ocb_spans(uint64_t *spans, int max);
+
 /* ---- ChaCha20, Poly1305, ChaCha20-Poly1305 (RFC 8439) ----------------------
  * The IETF layout: a 32-byte key, a 12-byte nonce, a 32-bit block counter
  * (state word 12).  key, nonce and aad are HOST memory; the data is device

@@ -85,6 +85,20 @@ class OtcGcmKey(ctypes.Structure):
     _fields_ = [("enc", OtcAesKey), ("h", ctypes.c_uint8 * 16)]
 
 
+class AesOcbContext(ctypes.Structure):
+    """Mirror of ``aes_ocb_context`` {enc, dec, l_star, l_dollar, l[33]} (aes.h)."""
+
+    _fields_ = [("enc", AesContext), ("dec", AesContext), ("l_star", ctypes.c_uint8 * 16),
+                ("l_dollar", ctypes.c_uint8 * 16), ("l", (ctypes.c_uint8 * 16) * 33)]
+
+
+class OtcOcbKey(ctypes.Structure):
+    """Mirror of ``otc_ocb_key`` (otc.h): K's two schedules, L_*, L_$ and L_0..L_32."""
+
+    _fields_ = [("enc", OtcAesKey), ("dec", OtcAesKey), ("l_star", ctypes.c_uint8 * 16),
+                ("l_dollar", ctypes.c_uint8 * 16), ("l", (ctypes.c_uint8 * 16) * 33)]
+
+
 class Arc4Context(ctypes.Structure):
     """Mirror of ``arc4_context`` {x, y, m[256]} (reference arc4.h:35-41)."""
 
@@ -167,6 +181,13 @@ def _declare_cpu(lib):
         "aes_crypt_ctr32": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_crypt_gcm": (c_int, [P(AesGcmContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_gcm_auth_decrypt": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
+        "aes_ocb_setkey": (c_int, [P(AesOcbContext), c_u8p, ctypes.c_uint]),
+        "aes_ocb_offset0": (c_int, [P(AesOcbContext), c_u8p, c_sz, c_sz, c_u8p]),
+        "aes_ocb_offset": (None, [P(AesOcbContext), c_u8p, c_u64, c_u8p]),
+        "aes_ocb_hash": (None, [P(AesOcbContext), c_u8p, c_sz, c_u8p]),
+        "aes_crypt_ocb_blocks": (c_int, [P(AesOcbContext), c_int, c_u8p, c_u64, c_u64, c_u8p, c_u8p, c_u8p]),
+        "aes_crypt_ocb": (c_int, [P(AesOcbContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_sz]),
+        "aes_ocb_auth_decrypt": (c_int, [P(AesOcbContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
         "chacha20_block": (None, [c_u8p, c_u8p, ctypes.c_uint32, c_u8p]),
         "chacha20_crypt": (c_int, [c_u8p, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_sz]),
         "poly1305_mac": (None, [c_u8p, c_u8p, c_sz, c_u8p]),
@@ -239,6 +260,10 @@ def _declare_gpu(lib):
         "otc_ghash_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
         "otc_aes_gcm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u64, c_int, c_sz, P(OtcGcmKey), c_vp, c_vp, c_int,
                                       c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
+        "otc_ocb_key_init": (c_int, [P(OtcOcbKey), c_u8p, c_int]),
+        "otc_aes_ocb": (c_int, [c_vp, c_vp, c_sz, P(OtcOcbKey), c_int, c_u8p, c_sz, c_u8p, c_sz, c_int, c_vp, c_vp]),
+        "otc_aes_ocb_blocks": (c_int, [c_vp, c_vp, c_u64, P(OtcOcbKey), c_int, c_u8p, c_u64, c_vp, c_vp]),
+        "otc_ocb_spans": (c_int, [P(c_u64), c_int]),
         "otc_chacha20": (c_int, [c_vp, c_vp, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_vp]),
         "otc_poly1305": (c_int, [c_vp, c_sz, c_u8p, c_vp, c_vp]),
         "otc_poly1305_spans": (c_int, [P(c_u64), c_int]),

@@ -131,6 +131,21 @@ class AES:
             return cpu_ref.cfb128_segments(self._key, iv, data, segment_bytes)
         return cpu_ref.serial_encrypt("cfb128", self._key, iv, data)
 
+    # ---- authenticated: AES-OCB3 (RFC 7253), one pass over the data ---------
+    def ocb_encrypt(self, data, nonce: bytes, aad: bytes = b"", out=None, tag_bytes: int = 16):
+        """``(ciphertext, tag)``: the nonce is 1 to 15 bytes and never reused
+        under this key, the tag ``tag_bytes`` (1 to 16) long."""
+        if isinstance(data, torch.Tensor):
+            return ops.ocb_ops.ocb_encrypt(data, self._key, nonce, aad, out=out, tag_bytes=tag_bytes)
+        return cpu_ref.ocb(self._key, nonce, data, aad, tag_bytes=tag_bytes)
+
+    def ocb_decrypt(self, data, nonce: bytes, tag, aad: bytes = b"", out=None):
+        """The plaintext; ``cpu_ref.OcbTagError`` -- with the output zeroed --
+        when the received ``tag`` (its length is the message's TAGLEN) does not match."""
+        if isinstance(data, torch.Tensor):
+            return ops.ocb_ops.ocb_decrypt(data, self._key, nonce, tag, aad, out=out)
+        return cpu_ref.ocb_auth_decrypt(self._key, nonce, data, tag, aad)
+
 
 class AESXTS:
     """XTS-AES (IEEE 1619) sector cipher: ``key`` is K1 || K2, 32 bytes

@@ -239,6 +239,121 @@ def gcm_auth_decrypt(key: bytes, iv: bytes, data: bytes, tag: bytes, aad: bytes 
     return bytes(out)[: len(data)]
 
 
+OCB_MAX_BYTES = 1 << 36  # RFC 7253 as this engine cuts it: block indices reach 2**32 (aes.h AES_OCB_MAX_BYTES)
+OCB_MAX_BLOCKS = 1 << 32
+
+
+class OcbTagError(ValueError):
+    """The tag of an AES-OCB3 message did not match; the plaintext was zeroed."""
+
+
+def _ocb_ctx(key: bytes) -> _native.AesOcbContext:
+    ctx = _native.AesOcbContext()
+    key = bytes(key)
+    if _native.cpu_lib().aes_ocb_setkey(ctypes.byref(ctx), _native.as_u8p(key), len(key) * 8):
+        raise ValueError("invalid AES key length")
+    return ctx
+
+
+def ocb_check(nonce: bytes, tag_bytes: int, nbytes: int = 0):
+    """What every OCB3 call checks of its nonce (1..15 bytes), its tag length
+    (1..16 bytes) and its message length: ValueError, as the device ops raise."""
+    if not 1 <= len(nonce) <= 15:
+        raise ValueError("an OCB nonce has 1 to 15 bytes")
+    if not isinstance(tag_bytes, int) or not 1 <= tag_bytes <= 16:
+        raise ValueError("an OCB tag has 1 to 16 bytes")
+    if nbytes > OCB_MAX_BYTES:
+        raise ValueError("an OCB message has at most 2**36 bytes")
+
+
+def ocb_check_blocks(first_block: int, nblocks: int):
+    if first_block < 0 or nblocks < 0 or first_block + nblocks > OCB_MAX_BLOCKS:
+        raise ValueError("OCB block indices reach at most 2**32")
+
+
+def ocb_l(key: bytes) -> dict:
+    """The key's constants: ``{"star": L_*, "dollar": L_$, "l": [L_0 .. L_32]}``."""
+    ctx = _ocb_ctx(key)
+    return {"star": bytes(ctx.l_star), "dollar": bytes(ctx.l_dollar), "l": [bytes(v) for v in ctx.l]}
+
+
+def ocb_offset0(key: bytes, nonce: bytes, tag_bytes: int = 16) -> bytes:
+    """Offset_0 of (nonce, tag length): RFC 7253's nonce block, Ktop, Stretch."""
+    nonce = bytes(nonce)
+    ocb_check(nonce, tag_bytes)
+    out = _buf(16)
+    _native.cpu_lib().aes_ocb_offset0(ctypes.byref(_ocb_ctx(key)), _native.as_u8p(nonce), len(nonce), tag_bytes, out)
+    return bytes(out)
+
+
+def ocb_offset(key: bytes, offset0: bytes, i: int) -> bytes:
+    """Offset_i by the closed form Offset_0 ^ XOR{L_j : bit j of i ^ (i >> 1)}, 0 <= i <= 2**32."""
+    ocb_check_blocks(i, 0)
+    out = _buf(16)
+    _native.cpu_lib().aes_ocb_offset(ctypes.byref(_ocb_ctx(key)), _native.as_u8p(_b16(offset0, "offset0")), i, out)
+    return bytes(out)
+
+
+def ocb_hash(key: bytes, aad: bytes) -> bytes:
+    """HASH(K, A) of RFC 7253; an empty A hashes to zero."""
+    aad, out = bytes(aad), _buf(16)
+    _native.cpu_lib().aes_ocb_hash(ctypes.byref(_ocb_ctx(key)), _native.as_u8p(aad), len(aad), out)
+    return bytes(out)
+
+
+def ocb_blocks(key: bytes, offset0: bytes, data: bytes, first_block: int = 0, checksum: bytes = bytes(16),
+               decrypt: bool = False):
+    """The whole blocks ``first_block + 1 ..`` of a message: ``(out, checksum)``,
+    the checksum continued from the one given."""
+    data = bytes(data)
+    if len(data) % 16:
+        raise ValueError("OCB blocks are 16 bytes")
+    ocb_check_blocks(first_block, len(data) // 16)
+    out = _buf(len(data))
+    cs = (ctypes.c_uint8 * 16).from_buffer_copy(_b16(checksum, "checksum"))
+    rc = _native.cpu_lib().aes_crypt_ocb_blocks(ctypes.byref(_ocb_ctx(key)), AES_DECRYPT if decrypt else AES_ENCRYPT,
+                                                _native.as_u8p(_b16(offset0, "offset0")), first_block, len(data) // 16,
+                                                _native.as_u8p(data), out, cs)
+    if rc:
+        raise ValueError("invalid OCB block range")
+    return bytes(out)[: len(data)], bytes(cs)
+
+
+def ocb(key: bytes, nonce: bytes, data: bytes, aad: bytes = b"", decrypt: bool = False, tag_bytes: int = 16):
+    """AES-OCB3 (RFC 7253) of one message: ``(out, tag)`` with the COMPUTED
+    ``tag_bytes``-long tag in both directions."""
+    ctx = _ocb_ctx(key)
+    nonce, data, aad = bytes(nonce), bytes(data), bytes(aad)
+    ocb_check(nonce, tag_bytes, len(data))
+    out, tag = _buf(len(data)), _buf(16)
+    rc = _native.cpu_lib().aes_crypt_ocb(ctypes.byref(ctx), AES_DECRYPT if decrypt else AES_ENCRYPT, len(data),
+                                         _native.as_u8p(nonce), len(nonce), _native.as_u8p(aad), len(aad),
+                                         _native.as_u8p(data), out, tag, tag_bytes)
+    if rc:
+        raise ValueError("invalid OCB lengths")
+    return bytes(out)[: len(data)], bytes(tag)[:tag_bytes]
+
+
+def ocb_auth_decrypt(key: bytes, nonce: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
+    """Authenticated decryption: TAGLEN is ``len(tag)``; compares in constant
+    time and raises OcbTagError (the C side zeroes its output) on a mismatch."""
+    ctx = _ocb_ctx(key)
+    nonce, data, aad, tag = bytes(nonce), bytes(data), bytes(aad), bytes(tag)
+    ocb_check(nonce, len(tag), len(data))
+    # not zero to begin with: err.output shows what the C side left on a mismatch
+    out = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(b"\xa5" * max(len(data), 1))
+    rc = _native.cpu_lib().aes_ocb_auth_decrypt(ctypes.byref(ctx), len(data), _native.as_u8p(nonce), len(nonce),
+                                                _native.as_u8p(aad), len(aad), _native.as_u8p(tag), len(tag),
+                                                _native.as_u8p(data), out)
+    if rc == -0x14:
+        err = OcbTagError("OCB tag mismatch")
+        err.output = bytes(out)[: len(data)]
+        raise err
+    if rc:
+        raise ValueError("invalid OCB lengths")
+    return bytes(out)[: len(data)]
+
+
 CHACHA_MAX_BYTES = ((1 << 32) - 1) * 64  # chacha.h CHACHA20_POLY1305_MAX_BYTES
 
 
