@@ -312,8 +312,8 @@ extern "C" int otc_aes_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *key
     /* large batches: claimed tile runs (first one handed out) instead of the
      * static split over the waves (A/B: OTC_BATCH_CLAIM_MIN_TILES) */
     static const uint64_t min_tiles = [] {
-        const char *v = getenv("OTC_BATCH_CLAIM_MIN_TILES");
-        return v && *v ? (uint64_t)strtoull(v, nullptr, 10) : (uint64_t)65536;
+        uint64_t v = 0;
+        return env_u64("OTC_BATCH_CLAIM_MIN_TILES", &v) ? v : (uint64_t)65536;
     }();
     const hipError_t e =
         ntiles >= min_tiles ? claim_alone(otc_impl::tt_ctr_batch_units(ntiles), 2, st, launch) : launch(nullptr);

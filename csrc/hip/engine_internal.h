@@ -69,6 +69,10 @@ inline uint64_t tile_map_fill(uint32_t *tile_msg, uint64_t *tile_first, size_t m
 int check_impl(int impl);
 /* CTR's choice (no split); ECB's and the decryptions' are made by job_run */
 int pick_impl(int impl, int bits, size_t ctr_bytes);
+/* a threshold variable: true and *out for a decimal number; unset or empty:
+ * false; anything else: false too, and one line on stderr (the callers read
+ * each variable once per process) */
+bool env_u64(const char *name, uint64_t *out);
 /* from these sizes the T-table runs as a persistent claim kernel */
 size_t tt_ctr_persistent_min();
 bool segenc_persistent(size_t nbytes, size_t nseg);

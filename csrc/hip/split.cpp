@@ -9,6 +9,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,6 +67,23 @@ int env_impl()
 }
 
 } // namespace
+
+bool env_u64(const char *name, uint64_t *out)
+{
+    const char *v = getenv(name);
+    if (!v || !*v) return false;
+    /* digits only, to the end: strtoull alone turns "abc" into 0 -- for a
+     * threshold, "every call" -- and takes "-1" and "12x" as numbers */
+    char *end = nullptr;
+    errno = 0;
+    const unsigned long long r = strtoull(v, &end, 10);
+    if (*v < '0' || *v > '9' || *end || errno == ERANGE) {
+        fprintf(stderr, "otc: ignoring %s=%s (expected a decimal number): the default holds\n", name, v);
+        return false;
+    }
+    *out = r;
+    return true;
+}
 
 int pick_impl(int impl, int bits, size_t ctr_bytes)
 {
@@ -319,11 +338,14 @@ hipError_t claim_snapshot(unsigned long long *ctr, uint64_t nunits, uint32_t pb,
  * (-4..+1.5%) (profiles/r6/xover/). */
 enum { FORM_SPLIT = 0, FORM_BS = 1, FORM_TT = 2 };
 /* OTC_TT_PERSISTENT_MIN_MIB / OTC_SEGENC_PERSISTENT_MIN_MIB: threshold
- * sweeps only (read once; unset = the measured defaults) */
+ * sweeps, and how the suite reaches the persistent kernels at small sizes
+ * (tests/test_gpu_claim_forms.py) (read once; unset = the measured defaults;
+ * a value too large for size_t: never) */
 size_t env_mib(const char *name, size_t dflt)
 {
-    const char *v = getenv(name);
-    return v && *v ? (size_t)strtoull(v, nullptr, 10) << 20 : dflt;
+    uint64_t mib = 0;
+    if (!env_u64(name, &mib)) return dflt;
+    return mib > (SIZE_MAX >> 20) ? SIZE_MAX : (size_t)mib << 20;
 }
 int split_form(int picked, size_t nbytes)
 {
