@@ -3,8 +3,9 @@
  * GHASH and AES-GCM (counter mode: engine.cpp's ctr32_run; hash: aes_gcm.hip),
  * AES-OCB3 (aes_ocb.hip),
  * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), batched GCM
- * (aes_gcm_batch.hip and the batched CTR kernel) and batched
- * ChaCha20-Poly1305 (chacha_batch.hip): the argument checks, what an
+ * (aes_gcm_batch.hip and the batched CTR kernel), batched
+ * ChaCha20-Poly1305 (chacha_batch.hip) and batched OCB3
+ * (aes_ocb_batch.hip): the argument checks, what an
  * op computes on the host (J0, the AAD's hash, the one-time key, the length
  * blocks) and the order of its launches.
  */
@@ -310,8 +311,8 @@ extern "C" int otc_chacha20_poly1305(const void *in, void *out, size_t nbytes, c
     return OTC_OK;
 }
 
-/* ---- what the two batched AEADs' planners share ----------------------------- */
-/* One record's buffers as otc_gcm_msg and otc_chacha_msg both hold them (in,
+/* ---- what the batched AEADs' planners share ----------------------------- */
+/* One record's buffers as otc_gcm_msg, otc_chacha_msg and otc_ocb_msg all hold them (in,
  * out, nbytes, aad, aad_bytes): what is wrong with them, or null. */
 template <class Msg>
 static const char *batch_record_fault(const Msg &d, uint64_t max_bytes, uint64_t max_aad, const char *too_big)
@@ -631,5 +632,73 @@ extern "C" int otc_chacha20_poly1305_batch(const otc_chacha_msg *msgs_dev, const
         if ((e = otc_impl::chacha_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
             return hip_fail(e, "chacha_batch wipe launch");
     }
+    return OTC_OK;
+}
+
+/* ---- batched AES-OCB3: many records, one key, own nonce and tag each --------- */
+extern "C" int otc_ocb_batch_spans(uint64_t *spans, int max) { return otc_impl::ocb_batch_spans(spans, spans ? max : 0); }
+
+extern "C" size_t otc_ocb_batch_ws_bytes(size_t nmsg) { return nmsg * 48; /* Offset_0[], checksum[], HASH[] */ }
+
+extern "C" int64_t otc_ocb_batch_plan(const otc_ocb_msg *msgs, size_t nmsg, uint32_t *tile_msg, uint64_t *tile_first)
+{
+    if (nmsg == 0) return 0;
+    if (!msgs) return set_err(OTC_ERR_ARG, "ocb_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "ocb_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "ocb_batch: record " + std::to_string(m) + ": " + what);
+    };
+    /* at most 65536 blocks: the kernels carry L_0 .. L_16 */
+    for (size_t m = 0; m < nmsg; ++m)
+        if (const char *f = batch_record_fault(msgs[m], OTC_OCB_BATCH_MAX_BYTES, OTC_OCB_BATCH_MAX_AAD,
+                                               "more than 1 MiB of data (use otc_aes_ocb)"))
+            return bad(m, f);
+    if (int r = batch_overlaps(msgs, nmsg, bad)) return r;
+    const uint64_t tile_blocks = 64; /* whole blocks only: the finisher takes the trailing bytes */
+    uint64_t t = 0;
+    for (size_t m = 0; m < nmsg; ++m)
+        t = tile_map_fill(tile_msg, tile_first, m, t, (msgs[m].nbytes / 16 + tile_blocks - 1) / tile_blocks);
+    return (int64_t)t;
+}
+
+extern "C" int otc_aes_ocb_batch(const otc_ocb_msg *msgs_dev, const uint32_t *tile_msg_dev,
+                                 const uint64_t *tile_first_dev, uint64_t ntiles, size_t nmsg, const otc_ocb_key *k,
+                                 int dir, const uint8_t *nonces_dev, void *tags_dev, const uint8_t *expect_dev,
+                                 uint8_t *ok_dev, void *ws_dev, void *stream)
+{
+    Range rg("otc_aes_ocb_batch");
+    if (int r = ocb_check_key(k, dir)) return r;
+    if (nmsg == 0) return OTC_OK;
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "ocb_batch: more than 2^32 - 1 records");
+    if (!msgs_dev || !tags_dev || !ws_dev) return set_err(OTC_ERR_ARG, "ocb_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "ocb_batch: misaligned descriptor array");
+    if ((uintptr_t)tags_dev & 15u) return set_err(OTC_ERR_ARG, "ocb_batch: the tag array must be 16-byte aligned");
+    if (ntiles && (!tile_msg_dev || !tile_first_dev)) return set_err(OTC_ERR_ARG, "ocb_batch: null tile map");
+    if (((uintptr_t)tile_first_dev & 7u) || ((uintptr_t)tile_msg_dev & 3u))
+        return set_err(OTC_ERR_ARG, "ocb_batch: misaligned tile map");
+    if ((uintptr_t)ws_dev & 15u) return set_err(OTC_ERR_ARG, "ocb_batch: the workspace must be 16-byte aligned");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "ocb_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * 16;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * 16 && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "ocb_batch: the expected tags overlap the computed tags or the verdicts");
+    }
+    if (!nonces_dev) return set_err(OTC_ERR_ARG, "ocb_batch: null nonces");
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+
+    hipError_t e = otc_impl::ocb_batch_prep(msgs_dev, nmsg, *k, nonces_dev, ws_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "ocb_batch prep launch");
+    e = otc_impl::ocb_batch_bulk(msgs_dev, nmsg, tile_msg_dev, tile_first_dev, ntiles, *k, !enc, ws_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "ocb_batch bulk launch");
+    e = otc_impl::ocb_batch_finish(msgs_dev, nmsg, *k, ws_dev, tags_dev, enc ? nullptr : expect_dev,
+                                   enc ? nullptr : ok_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "ocb_batch finish launch");
+    if (!enc && (e = otc_impl::ocb_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+        return hip_fail(e, "ocb_batch wipe launch");
     return OTC_OK;
 }

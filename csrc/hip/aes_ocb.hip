@@ -48,6 +48,7 @@
 #include "otc_device.h"
 #include "otc_kernels.h"
 #include "aes_tt_dev.h"
+#include "ocb_dev.h"
 
 using namespace otc_dev;
 
@@ -190,34 +191,6 @@ __global__ __launch_bounds__(64) void k_aes_ocb_clear(uint32_t *p)
     if (threadIdx.x < 4) p[threadIdx.x] = 0;
 }
 
-/* The forward cipher of one block on the constant tables in global memory
- * (1.25 KiB, L1 resident), for the finisher's two blocks */
-template <int NR>
-__device__ __forceinline__ void enc_block_global(const otc_aes_key &K, uint32_t (&s)[4])
-{
-    const uint32_t *te = g_tab.te0;
-    const uint8_t *sb = g_tab.sb;
-    uint32_t t[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[j] ^= K.rk[j];
-#pragma unroll
-    for (int r = 1; r < NR; ++r) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            t[j] = te[s[j] & 0xFFu] ^ rotl8(te[(s[(j + 1) & 3] >> 8) & 0xFFu]) ^
-                   rotl16(te[(s[(j + 2) & 3] >> 16) & 0xFFu]) ^ rotl24(te[s[(j + 3) & 3] >> 24]) ^ K.rk[4 * r + j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[j] = t[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        t[j] = ((uint32_t)sb[s[j] & 0xFFu] | (uint32_t)sb[(s[(j + 1) & 3] >> 8) & 0xFFu] << 8 |
-                (uint32_t)sb[(s[(j + 2) & 3] >> 16) & 0xFFu] << 16 | (uint32_t)sb[s[(j + 3) & 3] >> 24] << 24) ^
-               K.rk[4 * NR + j];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[j] = t[j];
-}
-
 struct OcbFinParams {
     const uint8_t *in;
     uint8_t *out;             /* the trailing piece: r bytes */
@@ -270,8 +243,6 @@ __global__ __launch_bounds__(64) void k_aes_ocb_fin(OcbFinParams P, otc_aes_key 
         P.tag[j] = (t[j] ^ P.hash[j]) & (k >= 4 ? 0xFFFFFFFFu : (1u << (8 * k)) - 1u);
     }
 }
-
-void words(uint32_t (&w)[4], const uint8_t b[16]) { memcpy(w, b, 16); }
 
 } // namespace
 

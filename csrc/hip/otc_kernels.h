@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_ocb.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
+ * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
  * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
@@ -199,6 +199,25 @@ hipError_t chacha20_batch_run(const otc_chacha_msg *msgs, const uint8_t *keys, c
  * the tag of a record that fails is zeroed.  lanes: CB_LANES_SHORT or _LONG */
 hipError_t poly1305_batch_run(const otc_chacha_msg *msgs, uint64_t nmsg, const void *otk, void *tags,
                               const uint8_t *expect, uint8_t *ok, bool hash_out, int lanes, hipStream_t st);
+
+/* ---- aes_ocb_batch.hip ---------------------------------------------------- */
+/* the bulk kernel's boundaries in bytes, smallest first; returns how many there are */
+int ocb_batch_spans(uint64_t *spans, int max);
+/* ws (16-byte aligned, 48 bytes per record): Offset_0[m] under (k, nonces[m]),
+ * a zero checksum[m], HASH(K, aad[m]) */
+hipError_t ocb_batch_prep(const otc_ocb_msg *msgs, uint64_t nmsg, const otc_ocb_key &k, const uint8_t *nonces, void *ws,
+                          hipStream_t st);
+/* the whole blocks of every record, tile by tile; their plaintexts' XOR into checksum[m] */
+hipError_t ocb_batch_bulk(const otc_ocb_msg *msgs, uint64_t nmsg, const uint32_t *tile_msg, const uint64_t *tile_first,
+                          uint64_t ntiles, const otc_ocb_key &k, bool dec, void *ws, hipStream_t st);
+/* the trailing bytes and tags[m]; with ok (a decryption), ok[m] = the tag equals
+ * expect[m], and the tag of a record that fails is zeroed */
+hipError_t ocb_batch_finish(const otc_ocb_msg *msgs, uint64_t nmsg, const otc_ocb_key &k, void *ws, void *tags,
+                            const uint8_t *expect, uint8_t *ok, hipStream_t st);
+inline hipError_t ocb_batch_wipe(const otc_ocb_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+{
+    return batch_wipe(msgs, nmsg, ok, st);
+}
 
 /* ---- stream_ops.hip ------------------------------------------------------ */
 hipError_t k_xor(const void *a, const void *b, void *out, size_t n, hipStream_t st);

@@ -564,6 +564,78 @@ int otc_chacha20_poly1305_batch(const otc_chacha_msg *msgs_dev, const uint32_t *
                                 int dir, const uint8_t *nonces_dev, void *tags_dev, const uint8_t *expect_dev,
                                 uint8_t *ok_dev, void *ws_dev, int lanes, void *stream);
 
+/* ---- batched AES-OCB3 ---------------------------------------------------------
+ * Many records under ONE key (otc_ocb_key: one key per batch, as for the
+ * batched GCM), each with its own 12-byte nonce, its own AAD and its own
+ * 16-byte tag: record m is RFC 7253 OCB3 with TAGLEN 128 under (key,
+ * nonces[m], aad[m]) and equals otc_aes_ocb on that record alone, byte for
+ * byte.  Other nonce and tag lengths stay with otc_aes_ocb.  OCB reads the data
+ * ONCE (the two other batched AEADs read it in the cipher pass and again in
+ * the hash pass); Offset_0 and HASH(K, A), which otc_aes_ocb computes on the
+ * host, are made on the device (csrc/hip/aes_ocb_batch.hip).
+ *
+ * Limits (the planner checks them on host copies of the descriptors): data
+ * 0 .. OTC_OCB_BATCH_MAX_BYTES per record, any byte count -- larger messages
+ * belong to otc_aes_ocb; AAD 0 .. OTC_OCB_BATCH_MAX_AAD, device memory, any
+ * alignment; data buffers 16-byte aligned; in == out allowed per record;
+ * distinct records must not overlap, no input may overlap another record's
+ * output, and no AAD may overlap any record's output.  A record of 0 bytes is
+ * valid, with AAD or without.
+ *
+ * The nonces are DEVICE data supplied to every run (n x 12 bytes): a replayed
+ * batch must bring new nonces, and nonce uniqueness under the key is the
+ * caller's duty.  A run is one linear chain of launches on `stream` -- no
+ * allocation, no host synchronisation, no second stream -- so it can be
+ * captured in a graph:
+ *   encrypt: prep -> bulk -> finish (tags)
+ *   decrypt: prep -> bulk -> finish (tags, verdicts) -> wipe
+ * prep writes every record's Offset_0 and HASH(K, A) into the workspace and
+ * clears its checksum; the bulk kernel takes the whole blocks, tile by tile,
+ * and collects the checksums; finish takes the trailing bytes and makes the
+ * tags.  OCB's checksum is over the plaintext, so a decryption decrypts before
+ * it can judge: every computed tag is compared on the device with expect_dev
+ * (n x 16; OR of the XORs, no early exit), ok_dev[m] becomes 1 or 0, and the
+ * output of every record with ok_dev[m] == 0 is zeroed (in place: the
+ * ciphertext with it), and so is its row of tags_dev.  expect_dev must not
+ * overlap tags_dev or ok_dev (rejected).  otc_last_impl: OTC_IMPL_TTABLE. */
+#define OTC_OCB_BATCH_MAX_BYTES (1u << 20)
+#define OTC_OCB_BATCH_MAX_AAD (1u << 16)
+typedef struct {
+    uint64_t in;        /* device addresses */
+    uint64_t out;
+    uint64_t nbytes;
+    uint64_t aad;
+    uint64_t aad_bytes; /* the five columns of otc_gcm_msg, on purpose: the wipe kernel serves all three */
+    uint64_t reserved;
+} otc_ocb_msg;
+
+/* Host planner over HOST copies of the descriptors: checks the caps, null
+ * pointers, the alignment, partial overlap of a record's in and out, overlap
+ * between records and of an AAD with any output; fills the tile map (a tile is
+ * 64 whole blocks, 1 KiB, of one record: ceil(nbytes / 16 / 64) tiles, none for
+ * a record under 16 bytes) -- either array may be NULL to only count.  Returns
+ * the number of tiles, or OTC_ERR_ARG with a message that names the record.
+ * Needs no device. */
+int64_t otc_ocb_batch_plan(const otc_ocb_msg *msgs, size_t nmsg, uint32_t *tile_msg, uint64_t *tile_first);
+/* the caller-owned workspace of a run: Offset_0[], checksum[] and HASH[], 16
+ * bytes per record each, 16-byte aligned */
+size_t otc_ocb_batch_ws_bytes(size_t nmsg);
+/* The bulk kernel's boundaries in BYTES, smallest first: a block, a slot (one
+ * tile), a wave pass (four slots), a workgroup step, the full grid's first
+ * step -- past it a workgroup takes a second step.  Writes up to max of them;
+ * returns the count. */
+int otc_ocb_batch_spans(uint64_t *spans, int max);
+/* nonces_dev: nmsg x 12 bytes, any alignment.  tags_dev: nmsg x 16, 16-byte
+ * aligned, the COMPUTED tags in both directions (decryption: zero for the
+ * records that fail); expect_dev (nmsg x 16, any alignment) / ok_dev:
+ * decryption only.  ws_dev: otc_ocb_batch_ws_bytes(nmsg), 16-byte aligned.
+ * The key, its L table and its round keys travel by value.  nmsg == 0 launches
+ * nothing; ntiles == 0 (no record has a whole block) skips the bulk kernel.
+ * Every bad argument is OTC_ERR_ARG before any HIP call. */
+int otc_aes_ocb_batch(const otc_ocb_msg *msgs_dev, const uint32_t *tile_msg_dev, const uint64_t *tile_first_dev,
+                      uint64_t ntiles, size_t nmsg, const otc_ocb_key *k, int dir, const uint8_t *nonces_dev,
+                      void *tags_dev, const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, void *stream);
+
 /* out = a ^ b (the device arc4_crypt combiner). */
 int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream);
 

@@ -264,6 +264,11 @@ def _declare_gpu(lib):
         "otc_aes_ocb": (c_int, [c_vp, c_vp, c_sz, P(OtcOcbKey), c_int, c_u8p, c_sz, c_u8p, c_sz, c_int, c_vp, c_vp]),
         "otc_aes_ocb_blocks": (c_int, [c_vp, c_vp, c_u64, P(OtcOcbKey), c_int, c_u8p, c_u64, c_vp, c_vp]),
         "otc_ocb_spans": (c_int, [P(c_u64), c_int]),
+        "otc_ocb_batch_plan": (ctypes.c_int64, [c_vp, c_sz, c_vp, c_vp]),
+        "otc_ocb_batch_ws_bytes": (c_sz, [c_sz]),
+        "otc_ocb_batch_spans": (c_int, [P(c_u64), c_int]),
+        "otc_aes_ocb_batch": (c_int, [c_vp, c_vp, c_vp, c_u64, c_sz, P(OtcOcbKey), c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp]),
         "otc_chacha20": (c_int, [c_vp, c_vp, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_vp]),
         "otc_poly1305": (c_int, [c_vp, c_sz, c_u8p, c_vp, c_vp]),
         "otc_poly1305_spans": (c_int, [P(c_u64), c_int]),

@@ -146,6 +146,17 @@ class AES:
             return ops.ocb_ops.ocb_decrypt(data, self._key, nonce, tag, aad, out=out)
         return cpu_ref.ocb_auth_decrypt(self._key, nonce, data, tag, aad)
 
+    def ocb_encrypt_batch(self, xs, nonces, aads=None, outs=None):
+        """Many GPU records at once, all under this key, each with its own
+        12-byte nonce (a device uint8 [n, 12] tensor) and AAD: ``(outs, tags)``
+        with 16-byte tags (``ops.ocb_batch_ops.OcbBatch``)."""
+        return ops.ocb_batch_ops.ocb_encrypt_batch(xs, self._key, nonces, aads=aads, outs=outs)
+
+    def ocb_decrypt_batch(self, xs, nonces, tags, aads=None, outs=None):
+        """``(outs, ok)``: ``ok`` is a device bool [n] tensor, and the output
+        of every record whose tag does not match is zeroed."""
+        return ops.ocb_batch_ops.ocb_decrypt_batch(xs, self._key, nonces, tags, aads=aads, outs=outs)
+
 
 class AESXTS:
     """XTS-AES (IEEE 1619) sector cipher: ``key`` is K1 || K2, 32 bytes

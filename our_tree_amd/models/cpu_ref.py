@@ -354,6 +354,19 @@ def ocb_auth_decrypt(key: bytes, nonce: bytes, data: bytes, tag: bytes, aad: byt
     return bytes(out)[: len(data)]
 
 
+def ocb_batch(key: bytes, nonces, datas, aads=None, decrypt: bool = False):
+    """The batched AES-OCB3 oracle: a loop over ``ocb``.  Record ``m`` is OCB3
+    under ``(key, nonces[m], aads[m])`` with a 12-byte nonce and a 16-byte
+    tag: a list of ``(out, tag)`` with the COMPUTED tags in both directions."""
+    nonces, datas = [bytes(n) for n in nonces], [bytes(d) for d in datas]
+    aads = [b""] * len(datas) if aads is None else [bytes(a) for a in aads]
+    if len(nonces) != len(datas) or len(aads) != len(datas):
+        raise ValueError("one nonce and one AAD per record")
+    if any(len(n) != 12 for n in nonces):
+        raise ValueError("a batched OCB nonce has 12 bytes")
+    return [ocb(key, n, d, a, decrypt=decrypt) for n, d, a in zip(nonces, datas, aads)]
+
+
 CHACHA_MAX_BYTES = ((1 << 32) - 1) * 64  # chacha.h CHACHA20_POLY1305_MAX_BYTES
 
 
