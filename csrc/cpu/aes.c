@@ -645,8 +645,12 @@ static void *ghash_worker(void *arg)
 
 /* Large calls (the device tests' oracle) hash T pieces of whole blocks on T
  * threads, piece 0 from y and the others from 0, and join them as
- * Y = sum P_t . H^(blocks after piece t). */
-void aes_ghash(const aes_gcm_context *ctx, unsigned char y[16], const unsigned char *data, size_t len)
+ * Y = sum P_t . H^(blocks after piece t).  mul is the product that ctx's
+ * tables are of: GHASH's, or POLYVAL's dot. */
+typedef void (*hash_mul_fn)(unsigned char z[16], const unsigned char x[16], const unsigned char y[16]);
+
+static void hash_threaded(const aes_gcm_context *ctx, hash_mul_fn mul, unsigned char y[16], const unsigned char *data,
+                          size_t len)
 {
     enum { MAXT = 8 };
     if (len < ((size_t)4 << 20)) {
@@ -675,11 +679,16 @@ void aes_ghash(const aes_gcm_context *ctx, unsigned char y[16], const unsigned c
         memcpy(p, jobs[t].y, 16);
         memcpy(sq, ctx->h, 16);
         for (; after; after >>= 1) {
-            if (after & 1) aes_gf128_mul(p, p, sq);
-            aes_gf128_mul(sq, sq, sq);
+            if (after & 1) mul(p, p, sq);
+            mul(sq, sq, sq);
         }
         for (int i = 0; i < 16; ++i) y[i] ^= p[i];
     }
+}
+
+void aes_ghash(const aes_gcm_context *ctx, unsigned char y[16], const unsigned char *data, size_t len)
+{
+    hash_threaded(ctx, aes_gf128_mul, y, data, len);
 }
 
 static void gcm_inc32(unsigned char ctr[16])
@@ -759,6 +768,165 @@ int aes_gcm_auth_decrypt(aes_gcm_context *ctx, size_t length, const unsigned cha
     if (r) return r;
     unsigned diff = 0; /* every byte compared, whatever the earlier ones gave */
     for (size_t i = 0; i < tag_len; ++i) diff |= (unsigned)(t[i] ^ tag[i]);
+    if (diff) {
+        memset(output, 0, length);
+        return POLARSSL_ERR_GCM_AUTH_FAILED;
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------
+ * AES-GCM-SIV (RFC 8452), written from the RFC.  POLYVAL's field is
+ * x^128 + x^127 + x^126 + x^121 + 1 and a block is a LITTLE-endian 128-bit
+ * number: bit 0 of byte 0 is the coefficient of x^0, "times x" is a one-bit
+ * left shift of that number, and a bit shifted out of byte 15 is folded back
+ * as x^127 + x^126 + x^121 + 1 (0xC2 into byte 15, 0x01 into byte 0).  The
+ * product is dot(a, b) = a . b . x^-128.  Y . H goes through the same
+ * positional nibble tables as GHASH's (aes_gcm_context.tab, ghash_mul_h):
+ * tab[p][n] = dot(nibble n at nibble position p, H), each a sum of the
+ * products H . x^(i - 128); only the doubling and the bit order differ.
+ * ------------------------------------------------------------------------- */
+static void polyval_mulx(unsigned char v[16])
+{
+    const unsigned carry = v[15] >> 7;
+    for (int i = 15; i > 0; --i) v[i] = (unsigned char)((v[i] << 1) | (v[i - 1] >> 7));
+    v[0] = (unsigned char)(v[0] << 1);
+    if (carry) {
+        v[15] ^= 0xC2;
+        v[0] ^= 0x01;
+    }
+}
+
+void aes_polyval_dot(unsigned char z[16], const unsigned char x[16], const unsigned char y[16])
+{
+    unsigned char acc[16] = {0};
+    /* bit i of x adds y . x^i; every step divides by x, 128 times in all */
+    for (int i = 0; i < 128; ++i) {
+        if (x[i / 8] & (1u << (i % 8)))
+            for (int j = 0; j < 16; ++j) acc[j] ^= y[j];
+        const unsigned low = acc[0] & 1u;
+        for (int j = 0; j < 15; ++j) acc[j] = (unsigned char)((acc[j] >> 1) | (acc[j + 1] << 7));
+        acc[15] >>= 1;
+        if (low) acc[15] ^= 0xE1; /* x^-1 = x^127 + x^126 + x^125 + x^120 */
+    }
+    memcpy(z, acc, 16);
+}
+
+/* ctx->tab for Y -> dot(Y, h); ctx->enc is left alone */
+static void polyval_set_h(aes_gcm_context *ctx, const unsigned char h[16])
+{
+    static const unsigned char one[16] = {1};
+    unsigned char p[128][16]; /* dot(x^i, H) = H . x^(i - 128) */
+    memcpy(ctx->h, h, 16);
+    aes_polyval_dot(p[0], h, one);
+    for (int i = 1; i < 128; ++i) {
+        memcpy(p[i], p[i - 1], 16);
+        polyval_mulx(p[i]);
+    }
+    for (int pos = 0; pos < 32; ++pos)
+        for (int n = 0; n < 16; ++n) {
+            /* nibble position 2 i is byte i's high nibble: powers 8 i + 4 .. 8 i + 7 */
+            const int base = 8 * (pos / 2) + (pos % 2 ? 0 : 4);
+            unsigned char e[16] = {0};
+            for (int k = 0; k < 4; ++k) /* the nibble's lowest bit is the lowest power */
+                if (n & (1 << k))
+                    for (int j = 0; j < 16; ++j) e[j] ^= p[base + k][j];
+            memcpy(ctx->tab[pos][n], e, 16);
+        }
+}
+
+void aes_polyval(const unsigned char h[16], unsigned char y[16], const unsigned char *data, size_t len)
+{
+    aes_gcm_context ctx;
+    polyval_set_h(&ctx, h);
+    hash_threaded(&ctx, aes_polyval_dot, y, data, len);
+}
+
+int aes_gcmsiv_derive(aes_context *kgk, const unsigned char nonce[12], unsigned char authkey[16],
+                      unsigned char enckey[32])
+{
+    if (kgk->nr != 10 && kgk->nr != 14) return POLARSSL_ERR_AES_INVALID_KEY_LENGTH;
+    const int enc_bytes = kgk->nr == 10 ? 16 : 32;
+    unsigned char in[16] = {0}, blk[16];
+    ensure_tables();
+    memcpy(in + 4, nonce, 12);
+    for (int i = 0; i < 2 + enc_bytes / 8; ++i) {
+        in[0] = (unsigned char)i; /* le32(i), i <= 5 */
+        encrypt_block(kgk, in, blk);
+        memcpy(i < 2 ? authkey + 8 * i : enckey + 8 * (i - 2), blk, 8);
+    }
+    return enc_bytes;
+}
+
+int aes_crypt_ctr_le32(aes_context *enc, size_t length, unsigned char ctr[16], const unsigned char *input,
+                       unsigned char *output)
+{
+    unsigned char ks[16];
+    ensure_tables();
+    while (length) {
+        const size_t n = length < 16 ? length : 16;
+        encrypt_block(enc, ctr, ks);
+        store_le32(ctr, load_le32(ctr) + 1u); /* wraps at 2^32; bytes 4..15 never change */
+        for (size_t i = 0; i < n; ++i) output[i] = (unsigned char)(input[i] ^ ks[i]);
+        input += n;
+        output += n;
+        length -= n;
+    }
+    return 0;
+}
+
+static void put64_le(unsigned char *p, uint64_t v)
+{
+    for (int i = 0; i < 8; ++i) p[i] = (unsigned char)(v >> (8 * i));
+}
+
+int aes_crypt_gcmsiv(aes_context *kgk, int mode, size_t length, const unsigned char nonce[12],
+                     const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                     const unsigned char *tag_in, unsigned char tag[16])
+{
+    if ((uint64_t)length > AES_GCM_SIV_MAX_BYTES || (uint64_t)aad_len > AES_GCM_SIV_MAX_BYTES)
+        return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    if (mode == AES_DECRYPT && !tag_in) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    unsigned char authkey[16], enckey[32], ctr[16], s[16] = {0}, lb[16];
+    const int enc_bytes = aes_gcmsiv_derive(kgk, nonce, authkey, enckey);
+    if (enc_bytes < 0) return enc_bytes;
+    aes_context enc;
+    aes_setkey_enc(&enc, enckey, (unsigned)enc_bytes * 8);
+    ensure_tables();
+    /* a decryption runs the counter mode from the RECEIVED tag, then hashes
+     * the plaintext it gave; an encryption hashes first: in place both ways */
+    if (mode == AES_DECRYPT) {
+        memcpy(ctr, tag_in, 16);
+        ctr[15] |= 0x80;
+        aes_crypt_ctr_le32(&enc, length, ctr, input, output);
+    }
+    const unsigned char *pt = mode == AES_DECRYPT ? output : input;
+    aes_polyval(authkey, s, aad, aad_len);
+    aes_polyval(authkey, s, pt, length);
+    put64_le(lb, (uint64_t)aad_len * 8);
+    put64_le(lb + 8, (uint64_t)length * 8);
+    aes_polyval(authkey, s, lb, 16);
+    for (int i = 0; i < 12; ++i) s[i] ^= nonce[i];
+    s[15] &= 0x7F;
+    encrypt_block(&enc, s, s);
+    if (mode != AES_DECRYPT) {
+        memcpy(ctr, s, 16);
+        ctr[15] |= 0x80;
+        aes_crypt_ctr_le32(&enc, length, ctr, input, output);
+    }
+    memcpy(tag, s, 16);
+    return 0;
+}
+
+int aes_gcmsiv_auth_decrypt(aes_context *kgk, size_t length, const unsigned char nonce[12], const unsigned char *aad,
+                            size_t aad_len, const unsigned char tag[16], const unsigned char *input,
+                            unsigned char *output)
+{
+    unsigned char t[16];
+    const int r = aes_crypt_gcmsiv(kgk, AES_DECRYPT, length, nonce, aad, aad_len, input, output, tag, t);
+    if (r) return r;
+    unsigned diff = 0; /* every byte compared, whatever the earlier ones gave */
+    for (int i = 0; i < 16; ++i) diff |= (unsigned)(t[i] ^ tag[i]);
     if (diff) {
         memset(output, 0, length);
         return POLARSSL_ERR_GCM_AUTH_FAILED;
@@ -1114,6 +1282,76 @@ const char *aes_monte_carlo_expected(int mode, int bits)
     }
 }
 
+/* RFC 8452 appendix A (POLYVAL, the derivation) and appendix C (sealed
+ * outputs: ciphertext || tag); the last two rows are from an independent model
+ * of the RFC: key 00.., nonce a0..ab, AAD bytes 100..120, plaintext bytes 1..49 */
+static const char *SIV_VEC[][5] = {
+    /* key, nonce, aad, plaintext, ciphertext || tag */
+    {"01000000000000000000000000000000", "030000000000000000000000", "", "", "dc20e2d83f25705bb49e439eca56de25"},
+    {"01000000000000000000000000000000", "030000000000000000000000", "", "0100000000000000",
+     "b5d839330ac7b786578782fff6013b815b287c22493a364c"},
+    {"01000000000000000000000000000000", "030000000000000000000000", "01", "0200000000000000",
+     "1e6daba35669f4273b0a1a2560969cdf790d99759abd1508"},
+    {"0100000000000000000000000000000000000000000000000000000000000000", "030000000000000000000000", "", "",
+     "07f5f4169bbf55a8400cd47ea6fd400f"},
+    {"0100000000000000000000000000000000000000000000000000000000000000", "030000000000000000000000", "",
+     "0100000000000000", "c2ef328e5c71c83b843122130f7364b761e0b97427e3df28"},
+    {"000102030405060708090a0b0c0d0e0f", "a0a1a2a3a4a5a6a7a8a9aaab", NULL, NULL,
+     "65483eb7d1533466ead8e673d7270e99ea4ffe611498a5f768131b4cd04e371ea2cdcbb60c093766b35139add04a79ddf740928eb78fabb"
+     "f8f4ee555ae38f2d815"},
+    {"000102030405060708090a0b0c0d0e0f101112131415161718191a1b1c1d1e1f", "a0a1a2a3a4a5a6a7a8a9aaab", NULL, NULL,
+     "c2f39d921b077cbba73072360062d524e91677592a794769b8106c9d4dfbf643dbda8d4cac178311cf1ca57ec80cad12c052296c35a730a"
+     "ce425c50d199ebfd125"},
+};
+
+int aes_gcmsiv_self_test(int verbose)
+{
+    int fails = 0;
+    char name[64];
+    unsigned char key[32], nonce[12], aad[32], pt[64], ref[96], out[96], tag[16], h[16], y[16] = {0}, x[32];
+    aes_context kgk;
+
+    unhex("25629347589242761d31f826ba4b757b", h);
+    unhex("4f4f95668c83dfb6401762bb2d01a262d1a24ddd2721d006bbe45f20d3c9f362", x);
+    unhex("f7a3b47b846119fae5b7866cf5e5b77e", ref);
+    aes_polyval(h, y, x, 32);
+    fails += report(verbose, "RFC 8452 A POLYVAL", memcmp(y, ref, 16) == 0);
+
+    unhex("ee8e1ed9ff2540ae8f2ba9f50bc2f27c", key);
+    unhex("752abad3e0afb5f434dc4310", nonce);
+    aes_setkey_enc(&kgk, key, 128);
+    unsigned char ak[16], ek[32];
+    int ok = aes_gcmsiv_derive(&kgk, nonce, ak, ek) == 16;
+    unhex("310728d9911f1f3837b24316c3fab9a0", ref);
+    ok = ok && memcmp(ak, ref, 16) == 0;
+    unhex("a4c5ae6249963279c100be4d7e2c6edd", ref);
+    fails += report(verbose, "RFC 8452 A key derivation", ok && memcmp(ek, ref, 16) == 0);
+
+    for (size_t v = 0; v < sizeof SIV_VEC / sizeof SIV_VEC[0]; ++v) {
+        const size_t kl = unhex(SIV_VEC[v][0], key);
+        size_t al, n;
+        unhex(SIV_VEC[v][1], nonce);
+        if (SIV_VEC[v][2]) {
+            al = unhex(SIV_VEC[v][2], aad);
+            n = unhex(SIV_VEC[v][3], pt);
+        } else {
+            al = 21;
+            n = 49;
+            for (size_t i = 0; i < al; ++i) aad[i] = (unsigned char)(100 + i);
+            for (size_t i = 0; i < n; ++i) pt[i] = (unsigned char)(1 + i);
+        }
+        ok = unhex(SIV_VEC[v][4], ref) == n + 16;
+        aes_setkey_enc(&kgk, key, (unsigned)(kl * 8));
+        ok = ok && aes_crypt_gcmsiv(&kgk, AES_ENCRYPT, n, nonce, aad, al, pt, out, NULL, tag) == 0;
+        ok = ok && memcmp(out, ref, n) == 0 && memcmp(tag, ref + n, 16) == 0;
+        /* and back, in place */
+        ok = ok && aes_gcmsiv_auth_decrypt(&kgk, n, nonce, aad, al, tag, out, out) == 0 && memcmp(out, pt, n) == 0;
+        snprintf(name, sizeof name, "AES-GCM-SIV-%d vector #%d", (int)(kl * 8), (int)v + 1);
+        fails += report(verbose, name, ok);
+    }
+    return fails;
+}
+
 int aes_self_test(int verbose)
 {
     int fails = 0;
@@ -1205,6 +1443,7 @@ int aes_self_test(int verbose)
         snprintf(name, sizeof name, "RFC 3686 AES-CTR test vector #%d", v + 1);
         fails += report(verbose, name, memcmp(out, ref, n) == 0);
     }
+    fails += aes_gcmsiv_self_test(verbose);
     static const char *mc_name[4] = {"ECB", "ECB", "CBC", "CBC"};
     for (int mode = 0; mode < 4; ++mode)
         for (int k = 0; k < 3; ++k) {

@@ -114,6 +114,121 @@ extern "C" int otc_aes_gcm(const void *in, void *out, size_t nbytes, const otc_g
     return OTC_OK;
 }
 
+/* ---- POLYVAL, GCM-SIV's counter mode, AES-GCM-SIV (RFC 8452) ------------------ */
+extern "C" int otc_polyval_spans(uint64_t *spans, int max) { return otc_impl::polyval_spans(spans, spans ? max : 0); }
+
+extern "C" int otc_ctr_le32_spans(uint64_t *spans, int max) { return otc_impl::ctr_le32_spans(spans, spans ? max : 0); }
+
+extern "C" int otc_polyval(const void *data, size_t nbytes, const uint8_t h[16], const uint8_t y0[16], void *y_dev,
+                           void *stream)
+{
+    Range rg("otc_polyval");
+    if (!h || !y0 || !y_dev) return set_err(OTC_ERR_ARG, "null argument");
+    if ((uintptr_t)y_dev & 3u) return set_err(OTC_ERR_ARG, "polyval: the result must be 4-byte aligned");
+    if (nbytes > OTC_GCM_SIV_MAX_BYTES) return set_err(OTC_ERR_ARG, "polyval: more than 2^36 bytes");
+    if (nbytes && !data) return set_err(OTC_ERR_ARG, "polyval: null buffer");
+    if ((uintptr_t)data & 15u) return set_err(OTC_ERR_ARG, "polyval: device buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    void *ws = nullptr;
+    hipError_t e = otc_impl::polyval_ws_alloc(nbytes, st, &ws);
+    if (e != hipSuccess) return ws_fail(e, "polyval workspace", "polyval: no memory for the tables and partials");
+    e = otc_impl::polyval_run(data, nbytes, h, y0, nullptr, y_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, "polyval launch");
+    return OTC_OK;
+}
+
+/* [a, a + 16) meets [b, b + n) */
+static bool tag_overlaps(const void *a, const void *b, size_t n)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return n && x < y + n && y < x + 16;
+}
+
+extern "C" int otc_aes_ctr_le32(const void *in, void *out, size_t nbytes, const otc_aes_key *k, const void *ctr0_dev,
+                                void *stream)
+{
+    Range rg("otc_aes_ctr_le32");
+    if (int r = check_key(k, OTC_DIR_ENCRYPT)) return r;
+    if (!ctr0_dev || ((uintptr_t)ctr0_dev & 3u))
+        return set_err(OTC_ERR_ARG, "aes_ctr_le32: the counter block must be 4-byte aligned device memory");
+    if (nbytes > OTC_GCM_SIV_MAX_BYTES) return set_err(OTC_ERR_ARG, "aes_ctr_le32: more than 2^32 blocks");
+    if (int r = check_bufs(in, out, nbytes, true, "aes_ctr_le32")) return r;
+    if (tag_overlaps(ctr0_dev, out, nbytes)) return set_err(OTC_ERR_ARG, "aes_ctr_le32: the counter block lies in the output");
+    set_last_impl(OTC_IMPL_TTABLE);
+    const hipError_t e = otc_impl::ctr_le32_run(in, out, nbytes, *k, ctr0_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "aes_ctr_le32 launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_gcm_siv_key_init(otc_gcm_siv_key *k, const uint8_t *key, int keybits)
+{
+    if (!k || !key) return set_err(OTC_ERR_ARG, "null argument");
+    if (keybits != 128 && keybits != 256) return set_err(OTC_ERR_ARG, "gcm_siv: the key has 128 or 256 bits");
+    return otc_aes_key_init(&k->kgk, key, keybits, OTC_DIR_ENCRYPT);
+}
+
+extern "C" int otc_aes_gcm_siv(const void *in, void *out, size_t nbytes, const otc_gcm_siv_key *k, int dir,
+                               const uint8_t nonce[12], const uint8_t *aad, size_t aad_len, const void *tag_in_dev,
+                               void *tag_dev, void *stream)
+{
+    Range rg("otc_aes_gcm_siv");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->kgk, OTC_DIR_ENCRYPT)) return r;
+    if (k->kgk.nr != 10 && k->kgk.nr != 14) return set_err(OTC_ERR_ARG, "gcm_siv: the key has 128 or 256 bits");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (!nonce) return set_err(OTC_ERR_ARG, "gcm_siv: null nonce");
+    if (aad_len && !aad) return set_err(OTC_ERR_ARG, "gcm_siv: null aad");
+    if ((uint64_t)aad_len > OTC_GCM_SIV_MAX_BYTES) return set_err(OTC_ERR_ARG, "gcm_siv: the AAD has at most 2^36 bytes");
+    if (!tag_dev || ((uintptr_t)tag_dev & 3u))
+        return set_err(OTC_ERR_ARG, "gcm_siv: the tag must be 4-byte aligned device memory");
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+    if (!enc && (!tag_in_dev || ((uintptr_t)tag_in_dev & 3u)))
+        return set_err(OTC_ERR_ARG, "gcm_siv: decryption needs the received tag, 4-byte aligned device memory");
+    if ((uint64_t)nbytes > OTC_GCM_SIV_MAX_BYTES) return set_err(OTC_ERR_ARG, "gcm_siv: a message has at most 2^36 bytes");
+    if (int r = check_bufs(in, out, nbytes, true, "aes_gcm_siv")) return r;
+    /* the counter mode reads a tag while it writes out, and the hash reads in (out) before the tag is written */
+    if (tag_overlaps(tag_dev, out, nbytes) || tag_overlaps(tag_dev, in, nbytes) ||
+        (!enc && tag_overlaps(tag_in_dev, out, nbytes)))
+        return set_err(OTC_ERR_ARG, "gcm_siv: a tag lies in the data");
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+
+    /* what does not depend on the data, on the host: the nonce's two keys, the
+     * AAD's hash state, the length block */
+    aes_context kgk;
+    aes_import_rk32(&kgk, k->kgk.rk, k->kgk.nr);
+    uint8_t authkey[16], enckey[32], y0[16] = {0};
+    const int enc_bytes = aes_gcmsiv_derive(&kgk, nonce, authkey, enckey);
+    otc_aes_key ek;
+    if (enc_bytes < 0) return set_err(OTC_ERR_ARG, "gcm_siv: the key has 128 or 256 bits");
+    if (int r = otc_aes_key_init(&ek, enckey, enc_bytes * 8, OTC_DIR_ENCRYPT)) return r;
+    aes_polyval(authkey, y0, aad, aad_len);
+    otc_impl::SivTag siv{};
+    for (int i = 0; i < 8; ++i) {
+        siv.lenblock[i] = (uint8_t)(((uint64_t)aad_len * 8) >> (8 * i));
+        siv.lenblock[8 + i] = (uint8_t)(((uint64_t)nbytes * 8) >> (8 * i));
+    }
+    memcpy(siv.nonce, nonce, 12);
+    siv.enc = &ek;
+
+    /* the hash's memory first: a failure leaves out and the tag untouched */
+    void *ws = nullptr;
+    hipError_t e = otc_impl::polyval_ws_alloc(nbytes, st, &ws);
+    if (e != hipSuccess) return ws_fail(e, "gcm_siv workspace", "gcm_siv: no memory for the hash's tables and partials");
+    /* a decryption's counter mode starts at the RECEIVED tag, in device memory as it is */
+    if (!enc && (e = otc_impl::ctr_le32_run(in, out, nbytes, ek, tag_in_dev, st)) != hipSuccess) {
+        if (ws) (void)otc_dev::ws_free(ws, st);
+        return hip_fail(e, "gcm_siv ctr launch");
+    }
+    /* over the plaintext: in of an encryption, out of a decryption */
+    e = otc_impl::polyval_run(enc ? in : out, nbytes, authkey, y0, &siv, tag_dev, ws, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_siv hash launch");
+    /* an encryption's starts at the tag the finisher has just written */
+    if (enc && (e = otc_impl::ctr_le32_run(in, out, nbytes, ek, tag_dev, st)) != hipSuccess)
+        return hip_fail(e, "gcm_siv ctr launch");
+    return OTC_OK;
+}
+
 /* ---- AES-OCB3 (RFC 7253) ---------------------------------------------------- */
 extern "C" int otc_ocb_spans(uint64_t *spans, int max) { return otc_impl::ocb_spans(spans, spans ? max : 0); }
 

@@ -3,7 +3,8 @@
  * for both kernel files (aes_gcm.hip, aes_gcm_batch.hip): the multiplication
  * by a constant through its positional byte table, the doubling, and the
  * kernel that builds such tables.  Everything is file-local (an unnamed
- * namespace): each kernel file instantiates what it uses.
+ * namespace): each kernel file instantiates what it uses.  The chip-wide level
+ * kernel over such tables is in ghash_levels_dev.h.
  *
  * Bit order: the leftmost bit of a block (bit 7 of byte 0) is x^0, "times x"
  * is a right shift of the byte string, reduction by 0xE1 || 0^120 -- the same

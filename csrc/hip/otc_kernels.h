@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
+ * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
  * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
@@ -125,6 +125,32 @@ hipError_t ghash_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws);
  * behind its kernels, also when it fails. */
 hipError_t ghash_run(const void *data, uint64_t nbytes, const uint8_t h[16], const uint8_t y0[16],
                      const uint8_t *lenblock, const uint8_t *ekj0, void *out16, void *ws, hipStream_t st);
+
+/* ---- aes_gcm_siv.hip ----------------------------------------------------- */
+/* byte sizes of the POLYVAL decomposition's pieces (GHASH's), smallest first; returns how many there are */
+int polyval_spans(uint64_t *spans, int max);
+/* the per-call tables and partials of polyval_run over nbytes, stream-ordered
+ * (behind otc_fault_inject_alloc); *ws stays null for nbytes == 0 */
+hipError_t polyval_ws_alloc(uint64_t nbytes, hipStream_t st, void **ws);
+/* what turns the hash into the GCM-SIV tag: the length block, the nonce and
+ * the derived encryption key's schedule */
+struct SivTag {
+    uint8_t lenblock[16];
+    uint8_t nonce[12];
+    const otc_aes_key *enc;
+};
+/* out16 (device) = POLYVAL_h continued from y0 over nbytes of device data, or,
+ * with siv, the tag E(dot(Y ^ lenblock, H) ^ nonce, bit 127 cleared).  Frees
+ * ws behind its kernels, also when it fails. */
+hipError_t polyval_run(const void *data, uint64_t nbytes, const uint8_t h[16], const uint8_t y0[16], const SivTag *siv,
+                       void *out16, void *ws, hipStream_t st);
+/* byte sizes at which k_aes_ctr_le32 takes another path, smallest first (as ocb_spans) */
+int ctr_le32_spans(uint64_t *spans, int max);
+/* out = in ^ keystream of GCM-SIV's counter mode under K (an encryption
+ * schedule) from the counter block in the 16 device bytes at ctr0_dev
+ * (4-byte aligned), read in stream order; nbytes <= 2^36 */
+hipError_t ctr_le32_run(const void *in, void *out, uint64_t nbytes, const otc_aes_key &K, const void *ctr0_dev,
+                        hipStream_t st);
 
 /* ---- aes_gcm_batch.hip --------------------------------------------------- */
 /* lanes per record of the batched hash kernel's two forms */

@@ -128,6 +128,45 @@ int aes_gcm_auth_decrypt(aes_gcm_context *ctx, size_t length, const unsigned cha
                          const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
                          const unsigned char *input, unsigned char *output);
 
+/* AES-GCM-SIV (RFC 8452), written from the RFC: the nonce-misuse-resistant
+ * AEAD.  The caller's key is a key-GENERATING key (128 or 256 bits; `kgk` is
+ * its encryption schedule): every nonce (exactly 12 bytes) derives a POLYVAL
+ * key and an encryption key from it.  The tag is E(POLYVAL over AAD and
+ * PLAINTEXT, folded with the nonce), and the counter mode starts at the tag
+ * with bit 7 of byte 15 set; its counter is bytes 0..3, little-endian.  The
+ * tag is always 16 bytes; plaintext and AAD have at most 2^36 bytes each. */
+#define AES_GCM_SIV_MAX_BYTES (((uint64_t)1) << 36)
+/* z = dot(x, y) = x . y . x^-128 in POLYVAL's field and little-endian bit
+ * order; a bit loop, for constants */
+void aes_polyval_dot(unsigned char z[16], const unsigned char x[16], const unsigned char y[16]);
+/* y = POLYVAL under h continued from y over len bytes, the last partial block zero-padded */
+void aes_polyval(const unsigned char h[16], unsigned char y[16], const unsigned char *data, size_t len);
+/* RFC 8452 section 4: block i is E_K(le32(i) || nonce)[0:8]; blocks 0..1 are
+ * the authentication key, 2..3 (AES-128) or 2..5 (AES-256) the encryption
+ * key.  Returns the encryption key's bytes (16 or 32), or
+ * POLARSSL_ERR_AES_INVALID_KEY_LENGTH for a 192-bit schedule. */
+int aes_gcmsiv_derive(aes_context *kgk, const unsigned char nonce[12], unsigned char authkey[16],
+                      unsigned char enckey[32]);
+/* GCM-SIV's counter mode: bytes 0..3 of ctr increment little-endian and wrap
+ * at 2^32 without carry, bytes 4..15 never change; ctr is left at the next
+ * block's value */
+int aes_crypt_ctr_le32(aes_context *enc, size_t length, unsigned char ctr[16], const unsigned char *input,
+                       unsigned char *output);
+/* mode AES_ENCRYPT / AES_DECRYPT; tag: the COMPUTED tag in both directions.
+ * A decryption runs its counter mode from tag_in, the received tag (an
+ * encryption ignores it).  May run in place. */
+int aes_crypt_gcmsiv(aes_context *kgk, int mode, size_t length, const unsigned char nonce[12],
+                     const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                     const unsigned char *tag_in, unsigned char tag[16]);
+/* decrypts and compares the 16 tag bytes in constant time; on a mismatch
+ * output is zeroed and POLARSSL_ERR_GCM_AUTH_FAILED returned */
+int aes_gcmsiv_auth_decrypt(aes_context *kgk, size_t length, const unsigned char nonce[12], const unsigned char *aad,
+                            size_t aad_len, const unsigned char tag[16], const unsigned char *input,
+                            unsigned char *output);
+/* the RFC's POLYVAL, derivation and sealed vectors (part of aes_self_test);
+ * returns how many failed */
+int aes_gcmsiv_self_test(int verbose);
+
 /* AES-OCB3 (RFC 7253), written from the RFC (the reference has no
  * authenticated mode): one block-cipher call per block, the tag from an XOR of
  * the plaintext blocks.  Offset_i = Offset_0 ^ XOR{ L_j : bit j of i ^ (i >> 1) },

@@ -252,6 +252,57 @@ int otc_ghash(const void *data, size_t nbytes, const uint8_t h[16], const uint8_
  * kernel takes another path.  Writes up to max of them; returns the count. */
 int otc_ghash_spans(uint64_t *spans, int max);
 
+/* AES-GCM-SIV (RFC 8452) of ONE message in device memory, 128- or 256-bit
+ * keys: the AEAD that stays safe when a nonce repeats under a key (a repeat
+ * shows only whether two messages were equal).  The caller's key is a key-
+ * GENERATING key: every call derives the nonce's POLYVAL key and encryption
+ * key from it on the host (4 or 6 block encryptions and a key expansion) and
+ * hashes the AAD there; nonce (exactly 12 bytes) and aad are HOST memory.
+ * nbytes and aad_len are 0 .. 2^36 each; the tag is always 16 bytes.  dir is
+ * OTC_DIR_ENCRYPT or OTC_DIR_DECRYPT; tag_dev is 16 bytes of 4-byte aligned
+ * device memory that receive the COMPUTED tag in both directions.  The tag is
+ * also the counter mode's initial counter block, so it never leaves the
+ * device: an encryption's counter kernel reads it where the finisher wrote
+ * it, a decryption's reads the RECEIVED tag from tag_in_dev (16 bytes of
+ * 4-byte aligned device memory; an encryption ignores it) -- comparing the
+ * two is the caller's (ops.gcm_siv_ops.gcm_siv_decrypt does it with one
+ * readback).  The call does not synchronise and can be captured in a graph.
+ * Stream order: encrypt: POLYVAL over in, the finisher (tag_dev), the counter
+ * mode from tag_dev; decrypt: the counter mode from tag_in_dev, POLYVAL over
+ * out, the finisher.  In place works both ways; neither tag may lie in the
+ * data.  Buffers are 16-byte aligned.  The hash's per-call tables and
+ * partials are stream-ordered allocations made BEFORE anything is launched: a
+ * failure (otc_fault_inject_alloc covers it) leaves out and tag_dev
+ * untouched.  otc_last_impl: OTC_IMPL_TTABLE (there is one kernel family,
+ * csrc/hip/aes_gcm_siv.hip). */
+#define OTC_GCM_SIV_MAX_BYTES (((uint64_t)1) << 36)
+typedef struct {
+    otc_aes_key kgk; /* the key-generating key's encryption schedule */
+} otc_gcm_siv_key;
+int otc_gcm_siv_key_init(otc_gcm_siv_key *k, const uint8_t *key, int keybits /* 128 | 256 */);
+int otc_aes_gcm_siv(const void *in, void *out, size_t nbytes, const otc_gcm_siv_key *k, int dir,
+                    const uint8_t nonce[12], const uint8_t *aad, size_t aad_len, const void *tag_in_dev, void *tag_dev,
+                    void *stream);
+/* GCM-SIV's counter mode: bytes 0..3 of the counter block increment
+ * little-endian and wrap at 2^32 without carry, bytes 4..15 never change, and
+ * bit 7 of byte 15 is forced on.  The initial counter block is 16 bytes of
+ * 4-byte aligned DEVICE memory outside out, read in stream order -- what an
+ * earlier kernel on the stream wrote there is what counts.  k is an
+ * encryption schedule of any key size; nbytes is at most 2^32 blocks, so one
+ * launch covers the wrap. */
+int otc_aes_ctr_le32(const void *in, void *out, size_t nbytes, const otc_aes_key *k, const void *ctr0_dev,
+                     void *stream);
+/* y_dev[16] (device) = POLYVAL_h (RFC 8452 section 3) continued from y0 over
+ * nbytes (0 .. 2^36) of device data, 16-byte aligned, the last partial block
+ * zero-padded; h and y0 are host memory.  Parallel over the whole chip: GHASH's
+ * level kernel over tables in POLYVAL's convention. */
+int otc_polyval(const void *data, size_t nbytes, const uint8_t h[16], const uint8_t y0[16], void *y_dev, void *stream);
+/* otc_ghash_spans for POLYVAL (the same pieces), and otc_ocb_spans for the
+ * counter kernel (a lane's block, one load of a wave, a pass, a wave's run, a
+ * workgroup's chunk, the full grid's first step) */
+int otc_polyval_spans(uint64_t *spans, int max);
+int otc_ctr_le32_spans(uint64_t *spans, int max);
+
 /* AES-OCB3 (RFC 7253) of ONE message in device memory, 128/192/256-bit keys:
  * an AEAD in one pass -- one block-cipher call per block, the tag from an XOR
  * of the plaintext blocks (csrc/hip/aes_ocb.hip).  nbytes is 0 .. 2^36 (any

@@ -85,6 +85,12 @@ class OtcGcmKey(ctypes.Structure):
     _fields_ = [("enc", OtcAesKey), ("h", ctypes.c_uint8 * 16)]
 
 
+class OtcGcmSivKey(ctypes.Structure):
+    """Mirror of ``otc_gcm_siv_key`` (otc.h): the key-generating key's encryption schedule."""
+
+    _fields_ = [("kgk", OtcAesKey)]
+
+
 class AesOcbContext(ctypes.Structure):
     """Mirror of ``aes_ocb_context`` {enc, dec, l_star, l_dollar, l[33]} (aes.h)."""
 
@@ -181,6 +187,13 @@ def _declare_cpu(lib):
         "aes_crypt_ctr32": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_crypt_gcm": (c_int, [P(AesGcmContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p]),
         "aes_gcm_auth_decrypt": (c_int, [P(AesGcmContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
+        "aes_polyval_dot": (None, [c_u8p, c_u8p, c_u8p]),
+        "aes_polyval": (None, [c_u8p, c_u8p, c_u8p, c_sz]),
+        "aes_gcmsiv_derive": (c_int, [P(AesContext), c_u8p, c_u8p, c_u8p]),
+        "aes_crypt_ctr_le32": (c_int, [P(AesContext), c_sz, c_u8p, c_u8p, c_u8p]),
+        "aes_crypt_gcmsiv": (c_int, [P(AesContext), c_int, c_sz, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p]),
+        "aes_gcmsiv_auth_decrypt": (c_int, [P(AesContext), c_sz, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p]),
+        "aes_gcmsiv_self_test": (c_int, [c_int]),
         "aes_ocb_setkey": (c_int, [P(AesOcbContext), c_u8p, ctypes.c_uint]),
         "aes_ocb_offset0": (c_int, [P(AesOcbContext), c_u8p, c_sz, c_sz, c_u8p]),
         "aes_ocb_offset": (None, [P(AesOcbContext), c_u8p, c_u64, c_u8p]),
@@ -260,6 +273,12 @@ def _declare_gpu(lib):
         "otc_ghash_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
         "otc_aes_gcm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u64, c_int, c_sz, P(OtcGcmKey), c_vp, c_vp, c_int,
                                       c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
+        "otc_gcm_siv_key_init": (c_int, [P(OtcGcmSivKey), c_u8p, c_int]),
+        "otc_aes_gcm_siv": (c_int, [c_vp, c_vp, c_sz, P(OtcGcmSivKey), c_int, c_u8p, c_u8p, c_sz, c_vp, c_vp, c_vp]),
+        "otc_aes_ctr_le32": (c_int, [c_vp, c_vp, c_sz, K, c_vp, c_vp]),
+        "otc_polyval": (c_int, [c_vp, c_sz, c_u8p, c_u8p, c_vp, c_vp]),
+        "otc_polyval_spans": (c_int, [P(c_u64), c_int]),
+        "otc_ctr_le32_spans": (c_int, [P(c_u64), c_int]),
         "otc_ocb_key_init": (c_int, [P(OtcOcbKey), c_u8p, c_int]),
         "otc_aes_ocb": (c_int, [c_vp, c_vp, c_sz, P(OtcOcbKey), c_int, c_u8p, c_sz, c_u8p, c_sz, c_int, c_vp, c_vp]),
         "otc_aes_ocb_blocks": (c_int, [c_vp, c_vp, c_u64, P(OtcOcbKey), c_int, c_u8p, c_u64, c_vp, c_vp]),

@@ -239,6 +239,98 @@ def gcm_auth_decrypt(key: bytes, iv: bytes, data: bytes, tag: bytes, aad: bytes 
     return bytes(out)[: len(data)]
 
 
+GCM_SIV_MAX_BYTES = 1 << 36  # RFC 8452: plaintext and AAD each (aes.h AES_GCM_SIV_MAX_BYTES)
+
+
+class GcmSivTagError(ValueError):
+    """The tag of an AES-GCM-SIV message did not match; the plaintext was zeroed."""
+
+
+def polyval_dot(x: bytes, y: bytes) -> bytes:
+    """dot(x, y) = x . y . x^-128 in POLYVAL's field and little-endian bit order (RFC 8452 section 3)."""
+    z = _buf(16)
+    _native.cpu_lib().aes_polyval_dot(z, _native.as_u8p(_b16(x, "x")), _native.as_u8p(_b16(y, "y")))
+    return bytes(z)
+
+
+def polyval(h: bytes, data: bytes, y0: bytes = bytes(16)) -> bytes:
+    """POLYVAL under ``h`` continued from ``y0`` over ``data``; the last partial
+    block is zero-padded."""
+    y = (ctypes.c_uint8 * 16).from_buffer_copy(_b16(y0, "y0"))
+    data = bytes(data)
+    _native.cpu_lib().aes_polyval(_native.as_u8p(_b16(h, "h")), y, _native.as_u8p(data), len(data))
+    return bytes(y)
+
+
+def gcm_siv_check(key: bytes, nonce: bytes, nbytes: int = 0, aad_bytes: int = 0):
+    """What every GCM-SIV call checks of its key (16 or 32 bytes), its nonce
+    (exactly 12 bytes) and its lengths: ValueError, as the device ops raise."""
+    if len(key) not in (16, 32):
+        raise ValueError(f"an AES-GCM-SIV key has 16 or 32 bytes, got {len(key)}")
+    if len(nonce) != 12:
+        raise ValueError("an AES-GCM-SIV nonce has exactly 12 bytes")
+    if nbytes > GCM_SIV_MAX_BYTES or aad_bytes > GCM_SIV_MAX_BYTES:
+        raise ValueError("an AES-GCM-SIV message and its AAD have at most 2**36 bytes each")
+
+
+def gcm_siv_derive(key: bytes, nonce: bytes):
+    """RFC 8452 section 4: ``(authentication key, encryption key)`` of ``nonce`` under the key-generating ``key``."""
+    key, nonce = bytes(key), bytes(nonce)
+    gcm_siv_check(key, nonce)
+    ak, ek = _buf(16), _buf(32)
+    n = _native.cpu_lib().aes_gcmsiv_derive(ctypes.byref(_ctx(key)), _native.as_u8p(nonce), ak, ek)
+    return bytes(ak), bytes(ek)[:n]
+
+
+def ctr_le32(key: bytes, ctr: bytes, data: bytes) -> bytes:
+    """GCM-SIV's counter mode: only bytes 0..3 of ``ctr`` increment
+    (little-endian), wrapping at 2**32 without carry into byte 4.  ``ctr`` is
+    used as given: GCM-SIV passes the tag with bit 7 of byte 15 set."""
+    ctx = _ctx(key)
+    c = (ctypes.c_uint8 * 16).from_buffer_copy(_b16(ctr, "ctr"))
+    data = bytes(data)
+    out = _buf(len(data))
+    _native.cpu_lib().aes_crypt_ctr_le32(ctypes.byref(ctx), len(data), c, _native.as_u8p(data), out)
+    return bytes(out)[: len(data)]
+
+
+def gcm_siv(key: bytes, nonce: bytes, data: bytes, aad: bytes = b"", decrypt: bool = False, tag: bytes | None = None):
+    """AES-GCM-SIV (RFC 8452) of one message: ``(out, tag)`` with the COMPUTED
+    16-byte tag in both directions.  A decryption runs its counter mode from
+    ``tag``, the received one."""
+    key, nonce, data, aad = bytes(key), bytes(nonce), bytes(data), bytes(aad)
+    gcm_siv_check(key, nonce, len(data), len(aad))
+    tag_in = _b16(tag, "tag") if decrypt else bytes(16)
+    out, t = _buf(len(data)), _buf(16)
+    rc = _native.cpu_lib().aes_crypt_gcmsiv(ctypes.byref(_ctx(key)), AES_DECRYPT if decrypt else AES_ENCRYPT, len(data),
+                                            _native.as_u8p(nonce), _native.as_u8p(aad), len(aad), _native.as_u8p(data),
+                                            out, _native.as_u8p(tag_in), t)
+    if rc:
+        raise ValueError("invalid GCM-SIV lengths")
+    return bytes(out)[: len(data)], bytes(t)
+
+
+def gcm_siv_auth_decrypt(key: bytes, nonce: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
+    """Authenticated decryption: compares the 16-byte tag in constant time and
+    raises GcmSivTagError (the C side zeroes its output) on a mismatch."""
+    key, nonce, data, aad, tag = bytes(key), bytes(nonce), bytes(data), bytes(aad), bytes(tag)
+    gcm_siv_check(key, nonce, len(data), len(aad))
+    if len(tag) != 16:
+        raise ValueError("an AES-GCM-SIV tag has 16 bytes")
+    # not zero to begin with: err.output shows what the C side left on a mismatch
+    out = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(b"\xa5" * max(len(data), 1))
+    rc = _native.cpu_lib().aes_gcmsiv_auth_decrypt(ctypes.byref(_ctx(key)), len(data), _native.as_u8p(nonce),
+                                                   _native.as_u8p(aad), len(aad), _native.as_u8p(tag),
+                                                   _native.as_u8p(data), out)
+    if rc == -0x12:
+        err = GcmSivTagError("GCM-SIV tag mismatch")
+        err.output = bytes(out)[: len(data)]
+        raise err
+    if rc:
+        raise ValueError("invalid GCM-SIV lengths")
+    return bytes(out)[: len(data)]
+
+
 OCB_MAX_BYTES = 1 << 36  # RFC 7253 as this engine cuts it: block indices reach 2**32 (aes.h AES_OCB_MAX_BYTES)
 OCB_MAX_BLOCKS = 1 << 32
 

@@ -134,11 +134,16 @@ def _spans(native_name: str) -> list[int]:
 def _open_with_tag(tag, lengths, length_msg: str, run, exc, mismatch_msg: str) -> torch.Tensor:
     """Authenticated decryption: the received ``tag`` (bytes or a uint8 tensor)
     has one of ``lengths`` bytes; ``run() -> (out, computed tag)``, whose prefix
-    is compared in constant time; on a mismatch ``out`` is zeroed and ``exc`` raised."""
-    tag = bytes(tag.cpu().numpy().tobytes()) if isinstance(tag, torch.Tensor) else bytes(tag)
-    if len(tag) not in lengths:
+    is compared in constant time; on a mismatch ``out`` is zeroed and ``exc`` raised.
+    A tensor's bytes are read back behind ``run()``'s launches, not in front of them."""
+    on_dev = isinstance(tag, torch.Tensor)
+    if not on_dev:
+        tag = bytes(tag)
+    if (_nbytes(tag) if on_dev else len(tag)) not in lengths:
         raise ValueError(length_msg)
     out, t = run()
+    if on_dev:
+        tag = bytes(tag.cpu().numpy().tobytes())
     if not hmac.compare_digest(t.cpu().numpy().tobytes()[: len(tag)], tag):
         out.zero_()
         raise exc(mismatch_msg)
