@@ -4,8 +4,8 @@
  * AES-OCB3 (aes_ocb.hip),
  * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), batched GCM
  * (aes_gcm_batch.hip and the batched CTR kernel), batched
- * ChaCha20-Poly1305 (chacha_batch.hip) and batched OCB3
- * (aes_ocb_batch.hip): the argument checks, what an
+ * ChaCha20-Poly1305 (chacha_batch.hip), batched OCB3
+ * (aes_ocb_batch.hip) and batched GCM-SIV (aes_gcm_siv_batch.hip): the argument checks, what an
  * op computes on the host (J0, the AAD's hash, the one-time key, the length
  * blocks) and the order of its launches.
  */
@@ -815,5 +815,153 @@ extern "C" int otc_aes_ocb_batch(const otc_ocb_msg *msgs_dev, const uint32_t *ti
     if (e != hipSuccess) return hip_fail(e, "ocb_batch finish launch");
     if (!enc && (e = otc_impl::ocb_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
         return hip_fail(e, "ocb_batch wipe launch");
+    return OTC_OK;
+}
+
+/* ---- batched AES-GCM-SIV: many records, one key-generating key, own nonce each -- */
+extern "C" int otc_gcm_siv_batch_spans(uint64_t *spans, int max)
+{
+    return otc_impl::gcm_siv_batch_spans(spans, spans ? max : 0);
+}
+
+/* H_m[], S_m[], then an otc_aes_key per record: the derived keys */
+extern "C" size_t otc_gcm_siv_batch_ws_bytes(size_t nmsg) { return nmsg * (32 + sizeof(otc_aes_key)); }
+
+extern "C" int64_t otc_gcm_siv_batch_plan(const otc_gcm_msg *msgs, size_t nmsg, uint32_t *tile_msg, uint64_t *tile_first)
+{
+    if (nmsg == 0) return 0;
+    if (!msgs) return set_err(OTC_ERR_ARG, "gcm_siv_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_siv_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "gcm_siv_batch: record " + std::to_string(m) + ": " + what);
+    };
+    /* at most 65536 blocks: the 32-bit counter passes no value twice within a record */
+    for (size_t m = 0; m < nmsg; ++m)
+        if (const char *f = batch_record_fault(msgs[m], OTC_GCM_SIV_BATCH_MAX_BYTES, OTC_GCM_SIV_BATCH_MAX_AAD,
+                                               "more than 1 MiB of data (use otc_aes_gcm_siv)"))
+            return bad(m, f);
+    if (int r = batch_overlaps(msgs, nmsg, bad)) return r;
+    const uint64_t tile_bytes = 16ull * OTC_GCM_SIV_BATCH_TILE_BLOCKS;
+    uint64_t t = 0;
+    for (size_t m = 0; m < nmsg; ++m)
+        t = tile_map_fill(tile_msg, tile_first, m, t, (msgs[m].nbytes + tile_bytes - 1) / tile_bytes);
+    return (int64_t)t;
+}
+
+/* 16 lanes per record unless the records are long.  A record never leaves its
+ * wave in either form (aes_gcm_siv_batch.hip), so per record the 16-lane form
+ * always costs fewer products: nb / 16 + 9 for four records against nb / 64 + 13
+ * for one.  What the 64-lane form buys is waves: a batch of few long records
+ * fills the chip only with one wave per record.  Measured on uniform batches of
+ * 64 MiB with a 13-byte AAD (docs/PERF.md "Batched AES-GCM-SIV"); the rule puts
+ * the change at a mean of 512 hashed blocks (8 KiB), ChaCha's value, whose fold
+ * has the same shape.  SUPPOSED, not measured: that the MEAN of a mixed batch
+ * decides, and that the record count does not enter. */
+extern "C" int otc_gcm_siv_batch_lanes(const otc_gcm_msg *msgs, size_t nmsg)
+{
+    uint64_t total = 0;
+    for (size_t m = 0; msgs && m < nmsg; ++m) total += (msgs[m].aad_bytes + 15) / 16 + (msgs[m].nbytes + 15) / 16 + 1;
+    return nmsg && total / nmsg > 512 ? otc_impl::GSB_LANES_LONG : otc_impl::GSB_LANES_SHORT;
+}
+
+static int gsb_lanes_ok(int &lanes)
+{
+    if (lanes == 0) lanes = otc_impl::GSB_LANES_LONG;
+    if (lanes != otc_impl::GSB_LANES_SHORT && lanes != otc_impl::GSB_LANES_LONG)
+        return set_err(OTC_ERR_ARG, "gcm_siv_batch: lanes must be 16 or 64 (0: 64)");
+    return OTC_OK;
+}
+
+extern "C" int otc_polyval_batch(const otc_gcm_msg *msgs_dev, size_t nmsg, const void *h_dev, void *s_dev, int lanes,
+                                 void *stream)
+{
+    Range rg("otc_polyval_batch");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = gsb_lanes_ok(lanes)) return r;
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_siv_batch: more than 2^32 - 1 records");
+    if (!msgs_dev || !h_dev || !s_dev) return set_err(OTC_ERR_ARG, "gcm_siv_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "gcm_siv_batch: misaligned descriptor array");
+    if (((uintptr_t)h_dev | (uintptr_t)s_dev) & 15u)
+        return set_err(OTC_ERR_ARG, "gcm_siv_batch: the key and hash arrays must be 16-byte aligned");
+    const hipError_t e = otc_impl::polyval_batch_run(msgs_dev, nmsg, h_dev, s_dev, false, lanes, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "polyval_batch launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_ctr_le32_batch(const otc_gcm_msg *msgs_dev, const otc_aes_key *keys_dev, const void *ctrs_dev,
+                                      const uint32_t *tile_msg_dev, const uint64_t *tile_first_dev, uint64_t ntiles,
+                                      size_t nmsg, int nr, void *stream)
+{
+    Range rg("otc_aes_ctr_le32_batch");
+    if (nr != 10 && nr != 12 && nr != 14) return set_err(OTC_ERR_ARG, "ctr_le32_batch: nr must be 10, 12 or 14");
+    if (nmsg == 0 || ntiles == 0) return OTC_OK;
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "ctr_le32_batch: more than 2^32 - 1 records");
+    if (!msgs_dev || !keys_dev || !ctrs_dev) return set_err(OTC_ERR_ARG, "ctr_le32_batch: null array");
+    if (!tile_msg_dev || !tile_first_dev) return set_err(OTC_ERR_ARG, "ctr_le32_batch: null tile map");
+    if ((((uintptr_t)msgs_dev | (uintptr_t)tile_first_dev) & 7u) || ((uintptr_t)tile_msg_dev & 3u))
+        return set_err(OTC_ERR_ARG, "ctr_le32_batch: misaligned descriptor arrays");
+    if ((uintptr_t)keys_dev & 15u) return set_err(OTC_ERR_ARG, "ctr_le32_batch: the schedules must be 16-byte aligned");
+    if ((uintptr_t)ctrs_dev & 3u) return set_err(OTC_ERR_ARG, "ctr_le32_batch: the counter blocks must be 4-byte aligned");
+    set_last_impl(OTC_IMPL_TTABLE);
+    const hipError_t e = otc_impl::ctr_le32_batch_run(msgs_dev, keys_dev, ctrs_dev, tile_msg_dev, tile_first_dev, ntiles,
+                                                      nr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "ctr_le32_batch launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_gcm_siv_batch(const otc_gcm_msg *msgs_dev, const uint32_t *tile_msg_dev,
+                                     const uint64_t *tile_first_dev, uint64_t ntiles, size_t nmsg,
+                                     const otc_gcm_siv_key *k, int dir, const uint8_t *nonces_dev, void *tags_dev,
+                                     const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, int lanes, void *stream)
+{
+    Range rg("otc_aes_gcm_siv_batch");
+    if (!k) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(&k->kgk, OTC_DIR_ENCRYPT)) return r;
+    if (k->kgk.nr != 10 && k->kgk.nr != 14) return set_err(OTC_ERR_ARG, "gcm_siv: the key has 128 or 256 bits");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (nmsg == 0) return OTC_OK;
+    if (int r = gsb_lanes_ok(lanes)) return r;
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_siv_batch: more than 2^32 - 1 records");
+    if (!msgs_dev || !tags_dev || !ws_dev) return set_err(OTC_ERR_ARG, "gcm_siv_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "gcm_siv_batch: misaligned descriptor array");
+    if ((uintptr_t)tags_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_siv_batch: the tag array must be 16-byte aligned");
+    if (ntiles && (!tile_msg_dev || !tile_first_dev)) return set_err(OTC_ERR_ARG, "gcm_siv_batch: null tile map");
+    if (((uintptr_t)tile_first_dev & 7u) || ((uintptr_t)tile_msg_dev & 3u))
+        return set_err(OTC_ERR_ARG, "gcm_siv_batch: misaligned tile map");
+    if ((uintptr_t)ws_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_siv_batch: the workspace must be 16-byte aligned");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "gcm_siv_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * 16;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * 16 && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "gcm_siv_batch: the expected tags overlap the computed tags or the verdicts");
+        if (e0 & 3u) return set_err(OTC_ERR_ARG, "gcm_siv_batch: the expected tags must be 4-byte aligned");
+    }
+    if (!nonces_dev) return set_err(OTC_ERR_ARG, "gcm_siv_batch: null nonces");
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+    const int nr = k->kgk.nr;
+    uint8_t *h = (uint8_t *)ws_dev, *s = h + nmsg * 16;
+    otc_aes_key *keys = (otc_aes_key *)(s + nmsg * 16);
+
+    hipError_t e = otc_impl::gcm_siv_batch_derive(k->kgk, nonces_dev, nmsg, h, keys, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_siv_batch derive launch");
+    /* the counter block of a record is its tag: the computed one, or a decryption's received one */
+    auto ctr = [&](const void *ctrs) {
+        return otc_impl::ctr_le32_batch_run(msgs_dev, keys, ctrs, tile_msg_dev, tile_first_dev, ntiles, nr, st);
+    };
+    if (!enc && (e = ctr(expect_dev)) != hipSuccess) return hip_fail(e, "gcm_siv_batch ctr launch");
+    /* over the plaintext: in of an encryption, out of a decryption */
+    if ((e = otc_impl::polyval_batch_run(msgs_dev, nmsg, h, s, !enc, lanes, st)) != hipSuccess)
+        return hip_fail(e, "gcm_siv_batch hash launch");
+    e = otc_impl::gcm_siv_batch_final(s, nonces_dev, keys, nmsg, nr, tags_dev, enc ? nullptr : expect_dev,
+                                      enc ? nullptr : ok_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_siv_batch finisher launch");
+    if (enc && (e = ctr(tags_dev)) != hipSuccess) return hip_fail(e, "gcm_siv_batch ctr launch");
+    if (!enc && (e = otc_impl::gcm_siv_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+        return hip_fail(e, "gcm_siv_batch wipe launch");
     return OTC_OK;
 }

@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
+ * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_siv_batch.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
  * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
@@ -241,6 +241,36 @@ hipError_t ocb_batch_bulk(const otc_ocb_msg *msgs, uint64_t nmsg, const uint32_t
 hipError_t ocb_batch_finish(const otc_ocb_msg *msgs, uint64_t nmsg, const otc_ocb_key &k, void *ws, void *tags,
                             const uint8_t *expect, uint8_t *ok, hipStream_t st);
 inline hipError_t ocb_batch_wipe(const otc_ocb_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+{
+    return batch_wipe(msgs, nmsg, ok, st);
+}
+
+/* ---- aes_gcm_siv_batch.hip ------------------------------------------------- */
+/* lanes per record of the batched POLYVAL kernel's two forms */
+constexpr int GSB_LANES_SHORT = 16, GSB_LANES_LONG = 64;
+/* the batched hash kernel's boundaries in hashed blocks, smallest first */
+int gcm_siv_batch_spans(uint64_t *spans, int max);
+/* per record: h[m] (nmsg x 16, 16-byte aligned) = the POLYVAL key and keys[m] =
+ * the expanded encryption key that kgk (nr 10 or 14) and nonces[m] derive */
+hipError_t gcm_siv_batch_derive(const otc_aes_key &kgk, const uint8_t *nonces, uint64_t nmsg, void *h, otc_aes_key *keys,
+                                hipStream_t st);
+/* s[m] (nmsg x 16, 16-byte aligned) = POLYVAL under h[m] of record m's padded AAD,
+ * padded data (its `out` with hash_out, else its `in`) and length block.
+ * lanes: GSB_LANES_SHORT or GSB_LANES_LONG per record */
+hipError_t polyval_batch_run(const otc_gcm_msg *msgs, uint64_t nmsg, const void *h, void *s, bool hash_out, int lanes,
+                             hipStream_t st);
+/* tags[m] = E_{keys[m]}((s[m] ^ nonces[m]) with bit 127 cleared); with ok (a
+ * decryption), ok[m] = the tag equals expect[m], and the tag of a record that
+ * fails is zeroed */
+hipError_t gcm_siv_batch_final(const void *s, const uint8_t *nonces, const otc_aes_key *keys, uint64_t nmsg, int nr,
+                               void *tags, const uint8_t *expect, uint8_t *ok, hipStream_t st);
+/* GCM-SIV's counter mode for every record, tile by tile (256 blocks): record m
+ * under keys[m] (nr rounds each) from the counter block ctrs[m] (nmsg x 16
+ * bytes, 4-byte aligned), both read in stream order */
+hipError_t ctr_le32_batch_run(const otc_gcm_msg *msgs, const otc_aes_key *keys, const void *ctrs,
+                              const uint32_t *tile_msg, const uint64_t *tile_first, uint64_t ntiles, int nr,
+                              hipStream_t st);
+inline hipError_t gcm_siv_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
 {
     return batch_wipe(msgs, nmsg, ok, st);
 }

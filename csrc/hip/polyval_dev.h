@@ -1,8 +1,9 @@
 /*
  * polyval_dev.h -- POLYVAL's field arithmetic (RFC 8452) as the device code of
- * aes_gcm_siv.hip uses it, in plain C callable on the host and on the device:
- * csrc/cpu/gcmsiv_selftest.c includes this file and runs the kernels'
- * decomposition with it against aes.c.
+ * aes_gcm_siv.hip and aes_gcm_siv_batch.hip uses it, in plain C callable on the
+ * host and on the device: csrc/cpu/gcmsiv_selftest.c and
+ * csrc/cpu/gcmsiv_batch_selftest.c include this file and run the kernels'
+ * decompositions with it against aes.c.
  *
  * A block is four little-endian words as loaded, which IS POLYVAL's order:
  * bit k of word j is the coefficient of x^(32 j + k).  "Times x" is a one-bit
@@ -71,6 +72,89 @@ PV_HD void siv_ctr_block(uint32_t c[4], const uint32_t t[4], uint32_t i)
     c[1] = t[1];
     c[2] = t[2];
     c[3] = t[3] | 0x80000000u;
+}
+
+/* ---- what the batched kernels add (aes_gcm_siv_batch.hip) --------------------
+ * A hash key per record rules the positional byte tables out (64 KiB per
+ * constant).  dot(a, C) = a . C . x^-128 needs no seed when it is taken as a
+ * Horner rule over a's 32 nibbles n_k, LOWEST first, that divides by x^4 at
+ * every step:  z = (z ^ n_k(x) . C) . x^-4,  k = 0 .. 31  -- n_0 is divided
+ * 32 times (x^-128), n_31 once (x^(124 - 128)).  The 16 products n(x) . C are
+ * the record's NIBBLE TABLE of C, 256 bytes.  Dividing is the clean direction
+ * in this field: x^-1 = x^127 + x^126 + x^125 + x^120 (aes.c aes_polyval_dot),
+ * so the four bits o that a right shift by 4 drops come back as
+ * clmul(o, 0xE1) << 117, which lies in word 3 alone (written as shifts of the
+ * nibble: as o . constant hipcc made it a quarter-rate v_mul_lo_u32 per step). */
+
+/* e = n(x) . C, n < 16: entry n of C's nibble table.  The nibble's lowest bit is the lowest power. */
+PV_HD void pv4_entry(uint32_t e[4], const uint32_t c[4], uint32_t n)
+{
+    uint32_t v[4] = {c[0], c[1], c[2], c[3]};
+    e[0] = e[1] = e[2] = e[3] = 0;
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t on = 0u - ((n >> k) & 1u);
+        for (int j = 0; j < 4; ++j) e[j] ^= v[j] & on;
+        pv_mulx(v);
+    }
+}
+
+/* nibble k (0 .. 31) of a */
+PV_HD uint32_t pv4_nibble(const uint32_t a[4], int k) { return (a[k >> 3] >> (4 * (k & 7))) & 15u; }
+
+/* one Horner step: z = (z ^ t) . x^-4, t the table entry of the step's nibble */
+PV_HD void pv4_step(uint32_t z[4], const uint32_t t[4])
+{
+    const uint32_t w0 = z[0] ^ t[0], w1 = z[1] ^ t[1], w2 = z[2] ^ t[2], w3 = z[3] ^ t[3];
+    const uint32_t o = w0 << 28; /* the dropped nibble at bits 28 .. 31: o . 0xE1 << 21 in shifts alone */
+    z[0] = w0 >> 4 | w1 << 28;
+    z[1] = w1 >> 4 | w2 << 28;
+    z[2] = w2 >> 4 | w3 << 28;
+    z[3] = (w3 >> 4) ^ o ^ (o >> 1) ^ (o >> 2) ^ (o >> 7);
+}
+
+/* z = dot(a, C) over C's nibble table (the host's form; the kernel reads the entries as uint4 from LDS) */
+PV_HD void pv4_dot(uint32_t z[4], const uint32_t a[4], const uint32_t (*tab)[4])
+{
+    uint32_t r[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 32; ++k) pv4_step(r, tab[pv4_nibble(a, k)]);
+    for (int j = 0; j < 4; ++j) z[j] = r[j];
+}
+
+/* RFC 8452 section 4: derivation block i of a nonce (three words as loaded) is le32(i) || nonce */
+PV_HD void siv_derive_block(uint32_t b[4], const uint32_t n[3], uint32_t i)
+{
+    b[0] = i;
+    b[1] = n[0];
+    b[2] = n[1];
+    b[3] = n[2];
+}
+
+PV_HD uint32_t siv_subword(uint32_t w, const uint8_t *sb)
+{
+    return (uint32_t)sb[w & 0xFFu] | (uint32_t)sb[(w >> 8) & 0xFFu] << 8 | (uint32_t)sb[(w >> 16) & 0xFFu] << 16 |
+           (uint32_t)sb[w >> 24] << 24;
+}
+
+/* FIPS-197 key expansion in otc_aes_key's convention (round key words as
+ * loaded little-endian, aes.c's): rk[0 .. nk) hold the key, nk = 4 or 8; fills
+ * rk[nk .. 4 (nk + 7)).  sb: the S-box.  The kernel calls it with a constant nk
+ * and the loop unrolls: the schedule stays in registers. */
+PV_HD void siv_expand_key(uint32_t *rk, const uint8_t *sb, const int nk)
+{
+    uint32_t rcon = 1;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = nk; i < 4 * (nk + 7); ++i) {
+        uint32_t t = rk[i - 1];
+        if (i % nk == 0) {
+            t = siv_subword(t >> 8 | t << 24, sb) ^ rcon;
+            rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11Bu : 0u);
+        } else if (nk == 8 && i % 8 == 4) {
+            t = siv_subword(t, sb);
+        }
+        rk[i] = rk[i - nk] ^ t;
+    }
 }
 
 #endif

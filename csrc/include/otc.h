@@ -687,6 +687,93 @@ int otc_aes_ocb_batch(const otc_ocb_msg *msgs_dev, const uint32_t *tile_msg_dev,
                       uint64_t ntiles, size_t nmsg, const otc_ocb_key *k, int dir, const uint8_t *nonces_dev,
                       void *tags_dev, const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, void *stream);
 
+/* ---- batched AES-GCM-SIV ------------------------------------------------------
+ * Many records under ONE key-generating key (otc_gcm_siv_key, 128 or 256 bits),
+ * each with its own 12-byte nonce, its own AAD and its own 16-byte tag: record m
+ * is RFC 8452 AES-GCM-SIV under (key, nonces[m], aad[m]) and equals
+ * otc_aes_gcm_siv on that record alone, byte for byte.  The shape the mode was
+ * made for -- many short records from senders that cannot coordinate nonces --
+ * and the one where otc_aes_gcm_siv's per-call cost (the derivation, a key
+ * expansion and the AAD's hash on the host, an allocation, 384 KiB of tables,
+ * four or more launches) is all there is.  In this mode the nonce decides both
+ * of a record's keys, so nothing per key is shared between records: the POLYVAL
+ * key H_m, the encryption key K_m and its schedule are made on the device, per
+ * record, and the hash multiplies on 256-byte tables that it builds per record
+ * in LDS (csrc/hip/aes_gcm_siv_batch.hip).
+ *
+ * Limits (the planner checks them on host copies of the descriptors): data
+ * 0 .. OTC_GCM_SIV_BATCH_MAX_BYTES per record, any byte count -- larger messages
+ * belong to otc_aes_gcm_siv; AAD 0 .. OTC_GCM_SIV_BATCH_MAX_AAD, device memory,
+ * any alignment; data buffers 16-byte aligned; in == out allowed per record;
+ * distinct records must not overlap, no input may overlap another record's
+ * output, and no AAD may overlap any record's output.  A record of 0 bytes is
+ * valid, with AAD or without.  The descriptor is otc_gcm_msg.
+ *
+ * The nonces are DEVICE data supplied to every run (n x 12 bytes).  A run is one
+ * linear chain of launches on `stream` -- no allocation, no host
+ * synchronisation, no second stream -- so it can be captured in a graph:
+ *   encrypt: derive -> batched POLYVAL over in -> finisher (tags)
+ *            -> batched CTR-LE32 from the tags
+ *   decrypt: derive -> batched CTR-LE32 from the RECEIVED tags
+ *            -> batched POLYVAL over out -> finisher (tags, verdicts) -> wipe
+ * The tag is the counter mode's initial counter block and never leaves the
+ * device.  GCM-SIV hashes the plaintext, so a decryption decrypts before it can
+ * judge: every computed tag is compared on the device with expect_dev (n x 16;
+ * all 16 bytes, OR of the XORs, no early exit), ok_dev[m] becomes 1 or 0, and the
+ * output of every record with ok_dev[m] == 0 is zeroed (in place: the ciphertext
+ * with it), and so is its row of tags_dev.  expect_dev must not overlap tags_dev
+ * or ok_dev (rejected).  otc_last_impl: OTC_IMPL_TTABLE. */
+#define OTC_GCM_SIV_BATCH_MAX_BYTES (1u << 20)
+#define OTC_GCM_SIV_BATCH_MAX_AAD (1u << 16)
+#define OTC_GCM_SIV_BATCH_TILE_BLOCKS 256 /* the counter kernel's tile: 4 KiB of one record */
+
+/* Host planner over HOST copies of the descriptors: checks the caps, null
+ * pointers, the alignment, partial overlap of a record's in and out, overlap
+ * between records and of an AAD with any output; fills the counter kernel's
+ * tile map (ceil(nbytes / 4096) tiles per record) -- either array may be NULL to
+ * only count.  Returns the number of tiles (records of 0 bytes have none), or
+ * OTC_ERR_ARG with a message that names the record.  Needs no device. */
+int64_t otc_gcm_siv_batch_plan(const otc_gcm_msg *msgs, size_t nmsg, uint32_t *tile_msg, uint64_t *tile_first);
+/* the caller-owned workspace of a run, 16-byte aligned: H_m[] and S_m[] (16
+ * bytes per record each), then every record's expanded encryption key (an
+ * otc_aes_key, 256 bytes).  It holds KEY MATERIAL after a run: the derived keys
+ * of every record -- the caller clears it when the batch is done with. */
+size_t otc_gcm_siv_batch_ws_bytes(size_t nmsg);
+/* How many lanes hash one record: 16 (four records per wave) or 64 (one wave per
+ * record).  Both compute the same; the choice is speed only.  From HOST copies
+ * of the descriptors (what the rule rests on: aead.cpp). */
+int otc_gcm_siv_batch_lanes(const otc_gcm_msg *msgs, size_t nmsg);
+/* The batched hash kernel's own boundaries in HASHED BLOCKS (AAD, data and
+ * length block together), smallest first: a pass of the 16-lane form (16), its
+ * batch of passes which is also a pass of the 64-lane form (64), a batch of
+ * those (256).  Writes up to max of them; returns the count. */
+int otc_gcm_siv_batch_spans(uint64_t *spans, int max);
+/* The hash by itself: s_dev[m] (nmsg x 16, 16-byte aligned) = POLYVAL under the
+ * key h_dev[m] (nmsg x 16, 16-byte aligned) of record m's pad16(AAD) ||
+ * pad16(`in` data) || le64(8 aad_bytes) le64(8 nbytes).  lanes: 16 or 64 (0: 64). */
+int otc_polyval_batch(const otc_gcm_msg *msgs_dev, size_t nmsg, const void *h_dev, void *s_dev, int lanes, void *stream);
+/* The counter mode by itself: record m's out = in ^ keystream under the
+ * encryption schedule keys_dev[m] (every one with nr rounds; 16-byte aligned)
+ * from the counter block ctrs_dev[m] (nmsg x 16 bytes, 4-byte aligned, outside
+ * every output), as otc_aes_ctr_le32 counts: bytes 0..3 little-endian modulo
+ * 2^32 without carry, bit 7 of byte 15 forced on.  Tile map from
+ * otc_gcm_siv_batch_plan. */
+int otc_aes_ctr_le32_batch(const otc_gcm_msg *msgs_dev, const otc_aes_key *keys_dev, const void *ctrs_dev,
+                           const uint32_t *tile_msg_dev, const uint64_t *tile_first_dev, uint64_t ntiles, size_t nmsg,
+                           int nr, void *stream);
+/* nonces_dev: nmsg x 12 bytes, any alignment.  tags_dev: nmsg x 16, 16-byte
+ * aligned, the COMPUTED tags in both directions (decryption: zero for the
+ * records that fail); expect_dev (nmsg x 16, 4-byte aligned: the counter kernel
+ * reads it) / ok_dev: decryption only.  ws_dev:
+ * otc_gcm_siv_batch_ws_bytes(nmsg), 16-byte aligned.  lanes: as
+ * otc_polyval_batch.  nmsg == 0 launches nothing; ntiles == 0 (all records
+ * empty) skips the counter kernel and still makes the tags.  Every bad argument
+ * is OTC_ERR_ARG before any HIP call. */
+int otc_aes_gcm_siv_batch(const otc_gcm_msg *msgs_dev, const uint32_t *tile_msg_dev, const uint64_t *tile_first_dev,
+                          uint64_t ntiles, size_t nmsg, const otc_gcm_siv_key *k, int dir, const uint8_t *nonces_dev,
+                          void *tags_dev, const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, int lanes,
+                          void *stream);
+
 /* out = a ^ b (the device arc4_crypt combiner). */
 int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream);
 

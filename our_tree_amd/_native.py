@@ -279,6 +279,14 @@ def _declare_gpu(lib):
         "otc_polyval": (c_int, [c_vp, c_sz, c_u8p, c_u8p, c_vp, c_vp]),
         "otc_polyval_spans": (c_int, [P(c_u64), c_int]),
         "otc_ctr_le32_spans": (c_int, [P(c_u64), c_int]),
+        "otc_gcm_siv_batch_plan": (ctypes.c_int64, [c_vp, c_sz, c_vp, c_vp]),
+        "otc_gcm_siv_batch_ws_bytes": (c_sz, [c_sz]),
+        "otc_gcm_siv_batch_lanes": (c_int, [c_vp, c_sz]),
+        "otc_gcm_siv_batch_spans": (c_int, [P(c_u64), c_int]),
+        "otc_polyval_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
+        "otc_aes_ctr_le32_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u64, c_sz, c_int, c_vp]),
+        "otc_aes_gcm_siv_batch": (c_int, [c_vp, c_vp, c_vp, c_u64, c_sz, P(OtcGcmSivKey), c_int, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_int, c_vp]),
         "otc_ocb_key_init": (c_int, [P(OtcOcbKey), c_u8p, c_int]),
         "otc_aes_ocb": (c_int, [c_vp, c_vp, c_sz, P(OtcOcbKey), c_int, c_u8p, c_sz, c_u8p, c_sz, c_int, c_vp, c_vp]),
         "otc_aes_ocb_blocks": (c_int, [c_vp, c_vp, c_u64, P(OtcOcbKey), c_int, c_u8p, c_u64, c_vp, c_vp]),

@@ -157,6 +157,19 @@ class AES:
         of every record whose tag does not match is zeroed."""
         return ops.ocb_batch_ops.ocb_decrypt_batch(xs, self._key, nonces, tags, aads=aads, outs=outs)
 
+    # ---- authenticated: batched AES-GCM-SIV (RFC 8452), nonce-misuse resistant ----
+    def gcm_siv_encrypt_batch(self, xs, nonces, aads=None, outs=None):
+        """Many GPU records at once, this key (16 or 32 bytes) as the
+        key-generating key, each record with its own 12-byte nonce (a device
+        uint8 [n, 12] tensor) and AAD: ``(outs, tags)`` with 16-byte tags
+        (``ops.gcm_siv_batch_ops.GcmSivBatch``)."""
+        return ops.gcm_siv_batch_ops.gcm_siv_encrypt_batch(xs, self._key, nonces, aads=aads, outs=outs)
+
+    def gcm_siv_decrypt_batch(self, xs, nonces, tags, aads=None, outs=None):
+        """``(outs, ok)``: ``ok`` is a device bool [n] tensor, and the output
+        of every record whose tag does not match is zeroed."""
+        return ops.gcm_siv_batch_ops.gcm_siv_decrypt_batch(xs, self._key, nonces, tags, aads=aads, outs=outs)
+
 
 class AESXTS:
     """XTS-AES (IEEE 1619) sector cipher: ``key`` is K1 || K2, 32 bytes

@@ -310,6 +310,19 @@ def gcm_siv(key: bytes, nonce: bytes, data: bytes, aad: bytes = b"", decrypt: bo
     return bytes(out)[: len(data)], bytes(t)
 
 
+def gcm_siv_batch(key: bytes, nonces, datas, aads=None, decrypt: bool = False, tags=None):
+    """The batched AES-GCM-SIV oracle: a loop over ``gcm_siv``.  Record ``m`` is
+    RFC 8452 under ``(key, nonces[m], aads[m])``: a list of ``(out, tag)`` with
+    the COMPUTED tags in both directions (a decryption starts its counter mode
+    from ``tags[m]``, the received one)."""
+    nonces, datas = [bytes(n) for n in nonces], [bytes(d) for d in datas]
+    aads = [b""] * len(datas) if aads is None else [bytes(a) for a in aads]
+    tags = [None] * len(datas) if tags is None else list(tags)
+    if len(nonces) != len(datas) or len(aads) != len(datas) or len(tags) != len(datas):
+        raise ValueError("one nonce, one AAD and one tag per record")
+    return [gcm_siv(key, n, d, a, decrypt=decrypt, tag=t) for n, d, a, t in zip(nonces, datas, aads, tags)]
+
+
 def gcm_siv_auth_decrypt(key: bytes, nonce: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
     """Authenticated decryption: compares the 16-byte tag in constant time and
     raises GcmSivTagError (the C side zeroes its output) on a mismatch."""
