@@ -37,14 +37,14 @@ OBJ    := build/obj
 
 CPU_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/rc4.c csrc/cpu/aesni.c csrc/cpu/numa.c csrc/cpu/rccl_plan.c csrc/cpu/chacha.c
 CPU_OBJ := $(patsubst csrc/cpu/%.c,$(OBJ)/cpu/%.o,$(CPU_SRC)) $(OBJ)/cpu/bs_selftest.o
-HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_ocb.hip csrc/hip/aes_ocb_batch.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_siv.hip csrc/hip/aes_gcm_siv_batch.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/chacha_batch.hip csrc/hip/stream_ops.hip
+HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_ocb.hip csrc/hip/aes_ocb_batch.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_siv.hip csrc/hip/aes_gcm_siv_batch.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_gcm_mk_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/chacha_batch.hip csrc/hip/stream_ops.hip
 HIP_OBJ := $(patsubst csrc/hip/%.hip,$(OBJ)/hip/%.o,$(HIP_SRC)) $(OBJ)/hip/engine.o $(OBJ)/hip/aead.o $(OBJ)/hip/runtime.o $(OBJ)/hip/split.o $(OBJ)/hip/pipeline.o
 
 BINS := bin/test bin/aes_test bin/aes_ecb_e bin/aes_ecb_d bin/otbench bin/bc_test
 
 .PHONY: all cpu clean
-all: $(LIBDIR)/libotc.so $(LIBDIR)/libotc_cpu.so $(BINS) bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest ref-o0
-cpu: $(LIBDIR)/libotc_cpu.so bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest ref-o0
+all: $(LIBDIR)/libotc.so $(LIBDIR)/libotc_cpu.so $(BINS) bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest ref-o0
+cpu: $(LIBDIR)/libotc_cpu.so bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest ref-o0
 
 $(OBJ)/cpu/aesni.o: csrc/cpu/aesni.c csrc/include/aesni.h
 	@mkdir -p $(dir $@)
@@ -150,6 +150,14 @@ bin/gcmsiv_batch_selftest: csrc/cpu/gcmsiv_batch_selftest.c csrc/hip/polyval_dev
 	@mkdir -p bin
 	$(CC) -O2 -g -std=gnu99 -Wall -Wextra $(INC) $< $(OBJ)/cpu/aes.o -o $@ -lpthread $(SANLD)
 
+# the many-key batched GCM kernels' arithmetic on the host (csrc/hip/polyval_dev.h: a
+# key's seven nibble tables from E_K(0), the lane decomposition of both forms with
+# byte-reversed blocks and its fold), against aes.c's GHASH and GCM
+# (tests/test_gcm_mk_batch_selftest_cpu.py also builds it with -fsanitize=address,undefined)
+bin/gcm_mk_batch_selftest: csrc/cpu/gcm_mk_batch_selftest.c csrc/hip/polyval_dev.h $(OBJ)/cpu/aes.o
+	@mkdir -p bin
+	$(CC) -O2 -g -std=gnu99 -Wall -Wextra $(INC) $< $(OBJ)/cpu/aes.o -o $@ -lpthread $(SANLD)
+
 bin/bc_test: csrc/cli/bc_test.cpp csrc/include/otc_cipher.hpp $(LIBDIR)/libotc.so
 	@mkdir -p bin
 	$(CXX) -O2 -std=c++17 -Wall $(INC) $< -o $@ -L$(LIBDIR) -lotc -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
@@ -195,7 +203,7 @@ bin/aes_test_o0: csrc/cli/aes_test.c $(O0_OBJ)
 	$(CXX) -O0 -g $(INC) -x c -std=gnu99 $< -x none $(O0_OBJ) -o $@ -lpthread
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
+	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
 
 # Host sanitizers over the threaded CPU paths (also tests/test_sanitizers_cpu.py)
 SAN_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/chacha.c csrc/cli/san_driver.c

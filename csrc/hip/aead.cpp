@@ -5,7 +5,8 @@
  * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), batched GCM
  * (aes_gcm_batch.hip and the batched CTR kernel), batched
  * ChaCha20-Poly1305 (chacha_batch.hip), batched OCB3
- * (aes_ocb_batch.hip) and batched GCM-SIV (aes_gcm_siv_batch.hip): the argument checks, what an
+ * (aes_ocb_batch.hip), batched GCM-SIV (aes_gcm_siv_batch.hip) and batched GCM
+ * with a key per record (aes_gcm_mk_batch.hip): the argument checks, what an
  * op computes on the host (J0, the AAD's hash, the one-time key, the length
  * blocks) and the order of its launches.
  */
@@ -963,5 +964,170 @@ extern "C" int otc_aes_gcm_siv_batch(const otc_gcm_msg *msgs_dev, const uint32_t
     if (enc && (e = ctr(tags_dev)) != hipSuccess) return hip_fail(e, "gcm_siv_batch ctr launch");
     if (!enc && (e = otc_impl::gcm_siv_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
         return hip_fail(e, "gcm_siv_batch wipe launch");
+    return OTC_OK;
+}
+
+/* ---- batched GCM, a key per record -------------------------------------------- */
+extern "C" int otc_gcm_mk_batch_spans(uint64_t *spans, int max)
+{
+    return otc_impl::gcm_mk_batch_spans(spans, spans ? max : 0);
+}
+
+extern "C" size_t otc_gcm_mk_batch_table_bytes(size_t nkeys) { return otc_impl::gcm_mk_batch_table_bytes(nkeys); }
+
+extern "C" size_t otc_gcm_mk_batch_ws_bytes(size_t nmsg) { return nmsg * 32; /* J0[], then the hashes */ }
+
+static bool gcm_mk_rounds(int nr) { return nr == 10 || nr == 12 || nr == 14; }
+
+extern "C" int otc_gcm_mk_batch_tables(const otc_aes_key *keys_dev, size_t nkeys, int nr, void *tab_dev, void *stream)
+{
+    Range rg("otc_gcm_mk_batch_tables");
+    if (!gcm_mk_rounds(nr)) return set_err(OTC_ERR_ARG, "gcm_mk_batch: nr must be 10, 12 or 14");
+    if (nkeys == 0) return OTC_OK;
+    if (!keys_dev || ((uintptr_t)keys_dev & 7u))
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: the schedules must be 8-byte aligned device memory");
+    if (!tab_dev || ((uintptr_t)tab_dev & 15u))
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: the tables must be 16-byte aligned device memory");
+    const hipError_t e = otc_impl::gcm_mk_batch_tables(keys_dev, nkeys, nr, tab_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gcm_mk_batch tables launch");
+    return OTC_OK;
+}
+
+extern "C" int64_t otc_gcm_mk_batch_plan(const otc_gcm_mk_msg *msgs, size_t nmsg, size_t nkeys, int tile_blocks,
+                                         otc_ctr_msg *ctr_msgs, uint32_t *tile_msg, uint64_t *tile_first)
+{
+    if (!check_tile_blocks(tile_blocks))
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: tile_blocks must be 64, 128 or 256");
+    if (nmsg == 0) return 0;
+    if (!msgs) return set_err(OTC_ERR_ARG, "gcm_mk_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_mk_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: record " + std::to_string(m) + ": " + what);
+    };
+    /* at most 65536 blocks: the counter's low 32 bits, started at 2, never wrap; an
+     * empty record has a key too (its tag comes from it) */
+    for (size_t m = 0; m < nmsg; ++m) {
+        if (msgs[m].key >= nkeys || msgs[m].key > 0xFFFFFFFFull) return bad(m, "key index out of range");
+        if (const char *f = batch_record_fault(msgs[m], OTC_GCM_BATCH_MAX_BYTES, OTC_GCM_BATCH_MAX_AAD,
+                                               "more than 1 MiB of data (use otc_aes_gcm)"))
+            return bad(m, f);
+    }
+    if (int r = batch_overlaps(msgs, nmsg, bad)) return r;
+    const uint64_t tile_bytes = 16ull * (uint64_t)tile_blocks;
+    uint64_t t = 0;
+    for (size_t m = 0; m < nmsg; ++m) {
+        const uint64_t nt = (msgs[m].nbytes + tile_bytes - 1) / tile_bytes;
+        if (ctr_msgs) ctr_msgs[m] = otc_ctr_msg{msgs[m].in, msgs[m].out, msgs[m].nbytes, 0, 0, (uint32_t)msgs[m].key, 0};
+        t = tile_map_fill(tile_msg, tile_first, m, t, nt);
+    }
+    return (int64_t)t;
+}
+
+/* 16 lanes per record for short records, 64 for long ones.  The fold is
+ * otc_gcm_siv_batch_lanes' (log2 L cross-lane steps, no serial chain, no
+ * workgroup barrier) and the rule started from that one's 512 hashed blocks.
+ * MEASURED for this kernel on uniform batches of 64 MiB, 256 keys, a 13-byte
+ * AAD (docs/PERF.md "Batched AES-GCM, a key per record", benchmarks/
+ * gcm_mk_batch.py --lanes-table), the hash alone: 16 lanes win at 1, 4 and 8 KiB
+ * records (66, 258 and 514 hashed blocks: x3.4, x2.0, x1.3), 64 lanes at 16 KiB
+ * (1026 blocks: x1.27); the whole encryption agrees at every size.  So 512 was
+ * too low here -- a record's copy of 5 tables costs less in front of the Horner
+ * passes than GCM-SIV's 4 squarings, which favours the 16-lane form longer --
+ * and the choice changes between 514 and 1026 blocks, where nothing was
+ * measured: 768 blocks (12 KiB) is where the rule puts it.  SUPPOSED, not
+ * measured: that the MEAN of a mixed batch decides -- no batch of mixed sizes
+ * has been timed. */
+extern "C" int otc_gcm_mk_batch_lanes(const otc_gcm_mk_msg *msgs, size_t nmsg)
+{
+    uint64_t total = 0;
+    for (size_t m = 0; msgs && m < nmsg; ++m) total += (msgs[m].aad_bytes + 15) / 16 + (msgs[m].nbytes + 15) / 16 + 1;
+    return nmsg && total / nmsg > 768 ? otc_impl::GMK_LANES_LONG : otc_impl::GMK_LANES_SHORT;
+}
+
+/* what otc_ghash_mk_batch and otc_aes_gcm_mk_batch check alike */
+static int gcm_mk_batch_common(const otc_gcm_mk_msg *msgs_dev, const void *tab_dev, const void *out16,
+                               const char *out_name, int &lanes)
+{
+    if (lanes == 0) lanes = otc_impl::GMK_LANES_LONG;
+    if (lanes != otc_impl::GMK_LANES_SHORT && lanes != otc_impl::GMK_LANES_LONG)
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: lanes must be 16 or 64 (0: 64)");
+    if (!msgs_dev || !tab_dev || !out16) return set_err(OTC_ERR_ARG, "gcm_mk_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "gcm_mk_batch: misaligned descriptor array");
+    if ((uintptr_t)tab_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_mk_batch: the tables must be 16-byte aligned");
+    if ((uintptr_t)out16 & 15u)
+        return set_err(OTC_ERR_ARG, std::string("gcm_mk_batch: ") + out_name + " must be 16-byte aligned");
+    return OTC_OK;
+}
+
+extern "C" int otc_ghash_mk_batch(const otc_gcm_mk_msg *msgs_dev, size_t nmsg, const void *tab_dev, void *s_dev,
+                                  int lanes, void *stream)
+{
+    Range rg("otc_ghash_mk_batch");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_mk_batch: more than 2^32 - 1 records");
+    if (int r = gcm_mk_batch_common(msgs_dev, tab_dev, s_dev, "the hash array", lanes)) return r;
+    if (nmsg == 0) return OTC_OK;
+    const hipError_t e = otc_impl::ghash_mk_batch_run(msgs_dev, nmsg, tab_dev, s_dev, false, lanes, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gcm_mk_batch hash launch");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_gcm_mk_batch(const otc_gcm_mk_msg *msgs_dev, otc_ctr_msg *ctr_msgs_dev,
+                                    const uint32_t *tile_msg_dev, const uint64_t *tile_first_dev, uint64_t ntiles,
+                                    int tile_blocks, size_t nmsg, const otc_aes_key *keys_dev, size_t nkeys, int nr,
+                                    const void *tab_dev, int dir, const uint8_t *ivs_dev, void *tags_dev,
+                                    const uint8_t *expect_dev, int tag_bytes, uint8_t *ok_dev, void *ws_dev, int lanes,
+                                    void *stream)
+{
+    Range rg("otc_aes_gcm_mk_batch");
+    if (!gcm_mk_rounds(nr)) return set_err(OTC_ERR_ARG, "gcm_mk_batch: nr must be 10, 12 or 14");
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (!check_tile_blocks(tile_blocks))
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: tile_blocks must be 64, 128 or 256");
+    if (tag_bytes < 4 || tag_bytes > 16) return set_err(OTC_ERR_ARG, "gcm_mk_batch: a tag has 4 to 16 bytes");
+    if (nmsg == 0) return OTC_OK;
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "gcm_mk_batch: more than 2^32 - 1 records");
+    if (nkeys == 0) return set_err(OTC_ERR_ARG, "gcm_mk_batch: no keys");
+    if (int r = gcm_mk_batch_common(msgs_dev, tab_dev, tags_dev, "the tag array", lanes)) return r;
+    if (!ctr_msgs_dev || !keys_dev || !ws_dev) return set_err(OTC_ERR_ARG, "gcm_mk_batch: null array");
+    if (ntiles && (!tile_msg_dev || !tile_first_dev)) return set_err(OTC_ERR_ARG, "gcm_mk_batch: null tile map");
+    if ((((uintptr_t)ctr_msgs_dev) | ((uintptr_t)keys_dev) | ((uintptr_t)tile_first_dev)) & 7u ||
+        ((uintptr_t)tile_msg_dev & 3u))
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: misaligned descriptor arrays");
+    if ((uintptr_t)ws_dev & 15u) return set_err(OTC_ERR_ARG, "gcm_mk_batch: the workspace must be 16-byte aligned");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "gcm_mk_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * (size_t)tag_bytes;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * 16 && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "gcm_mk_batch: the expected tags overlap the computed tags or the verdicts");
+    }
+    if (!ivs_dev) return set_err(OTC_ERR_ARG, "gcm_mk_batch: null IVs");
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+    uint8_t *j0 = (uint8_t *)ws_dev, *s = j0 + nmsg * 16;
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+
+    hipError_t e = otc_impl::gcm_batch_prep(ivs_dev, nmsg, ctr_msgs_dev, j0, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_mk_batch prep launch");
+    /* the CTR half: the batched kernel's static split, a key index per message */
+    auto ctr = [&] {
+        return ntiles ? otc_impl::tt_ctr_batch(ctr_msgs_dev, keys_dev, tile_msg_dev, tile_first_dev, ntiles, tile_blocks,
+                                               nr, st, nullptr)
+                      : hipSuccess;
+    };
+    if (enc && (e = ctr()) != hipSuccess) return hip_fail(e, "gcm_mk_batch ctr launch");
+    /* over the ciphertext: out of an encryption, in of a decryption */
+    if ((e = otc_impl::ghash_mk_batch_run(msgs_dev, nmsg, tab_dev, s, enc, lanes, st)) != hipSuccess)
+        return hip_fail(e, "gcm_mk_batch hash launch");
+    e = otc_impl::gcm_mk_batch_final(msgs_dev, keys_dev, j0, s, nmsg, nr, tags_dev, enc ? nullptr : expect_dev, tag_bytes,
+                                     enc ? nullptr : ok_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "gcm_mk_batch finisher launch");
+    if (!enc) {
+        if ((e = ctr()) != hipSuccess) return hip_fail(e, "gcm_mk_batch ctr launch");
+        if ((e = otc_impl::gcm_mk_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+            return hip_fail(e, "gcm_mk_batch wipe launch");
+    }
     return OTC_OK;
 }

@@ -45,7 +45,9 @@
  *   powers    C_s = H^(2^s), s = 0 .. log2 L, by squaring; the record's first 16
  *             lanes write one table entry each, every lane squares redundantly.
  *             (In the 16-lane form a record's lanes are one of the LDS's four
- *             service groups of a 16-byte read, not consecutive ones: sb_place.)
+ *             service groups of a 16-byte read, not consecutive ones: sb_place,
+ *             polyval_batch_dev.h, which holds what this hash kernel shares with
+ *             aes_gcm_mk_batch.hip's.)
  *   lanes     lane j runs Horner under H^L over the record's blocks L apart,
  *             aligned to the END of the record (zero blocks in front).
  *   fold      log2 L steps across lanes, A_j = A_j . H^d ^ A_{j+d}, d = 1, 2, ..
@@ -71,7 +73,7 @@
 #include "otc_kernels.h"
 #include "aes_tt_dev.h"
 #include "ocb_dev.h"
-#include "polyval_dev.h"
+#include "polyval_batch_dev.h"
 
 using namespace otc_dev;
 
@@ -79,7 +81,6 @@ namespace otc_impl {
 
 namespace {
 
-typedef const __attribute__((address_space(1))) uint8_t *gptr8;
 typedef __attribute__((address_space(1))) uint8_t g_u8;
 /* loads through the constant address space (wave-uniform address -> s_load), as aes_tt.hip's batch kernel */
 typedef const __attribute__((address_space(4))) uint32_t *cptr32;
@@ -137,38 +138,10 @@ __global__ __launch_bounds__(64) void k_gsb_derive(otc_aes_key KGK, const uint8_
 }
 
 /* ---- the batched hash -------------------------------------------------------- */
-constexpr uint32_t SB_THREADS = 256; /* 4 waves: they share nothing but the launch */
-constexpr uint32_t SB_BATCH = 4;     /* passes loaded ahead */
-
-/* one record as the hash sees it */
-struct SbRec {
-    gptr8 data, aad;
-    uint64_t nbytes, aad_bytes;
-    uint64_t na, nd; /* blocks of the AAD and of the data */
-};
-
-/* the 16 bytes at p + off, those at or past `end` as zero; never reads them
- * (aes_gcm_batch.hip's gb_bytes: that file's kernels stay as they are) */
-__device__ __forceinline__ uint4 sb_bytes(gptr8 p, uint64_t off, uint64_t end)
-{
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (uint32_t t = 0; t < 16; ++t) {
-        const uint32_t v = off + t < end ? (uint32_t)p[off + t] : 0u;
-        w[t >> 2] |= v << (8 * (t & 3));
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 /* block i (< na + nd + 1) of the record's hashed string */
 __device__ __forceinline__ uint4 sb_block(const SbRec &R, uint64_t i)
 {
-    if (i < R.na) return sb_bytes(R.aad, i * 16, R.aad_bytes); /* any alignment: bytes */
-    if (i < R.na + R.nd) {
-        const uint64_t off = (i - R.na) * 16;
-        if (off + 16 <= R.nbytes) return ld_u4<false, true>((const uint8_t *)R.data + off);
-        return sb_bytes(R.data, off, R.nbytes);
-    }
+    if (i < R.na + R.nd) return sb_text_block(R, i);
     const uint64_t ab = R.aad_bytes * 8, db = R.nbytes * 8; /* le64(8 aad) le64(8 n) */
     return make_uint4((uint32_t)ab, (uint32_t)(ab >> 32), (uint32_t)db, (uint32_t)(db >> 32));
 }
@@ -180,51 +153,6 @@ struct SbParams {
     uint4 *s;          /* nmsg x 16: S_m */
     uint32_t hash_out; /* hash the record's `out` (a decryption's plaintext), else its `in` */
 };
-
-/* dot(a, C) over C's nibble table T (LDS): every lookup's address comes from a alone */
-__device__ __forceinline__ uint4 sb_mul(const uint4 *T, uint4 a)
-{
-    const uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-    uint32_t z[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        const uint4 e = T[pv4_nibble(aw, k)];
-        const uint32_t t[4] = {e.x, e.y, e.z, e.w};
-        pv4_step(z, t);
-    }
-    return make_uint4(z[0], z[1], z[2], z[3]);
-}
-
-__device__ __forceinline__ uint4 sb_xor(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
-
-/* what one lane of a wave wrote to LDS, the wave's other lanes read after this: a
- * wave's LDS accesses execute in order, so only the compiler must keep them so */
-__device__ __forceinline__ void sb_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-/* The 16-lane form puts a record on one of the four 16-lane groups in which the LDS serves a
- * wave's ds_read_b128 -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- and not on
- * 16 consecutive lanes: lanes of one group then read ONE record's table, where two lanes either
- * take the same entry (one address, broadcast) or entries in different banks (an entry is 4 banks,
- * a table all 64).  On consecutive lanes a group mixes the tables of the wave's four records, which
- * lie on the same banks, and random nibbles collide about 3 deep.  sb_place: physical lane ->
- * record of the wave and lane of the record; sb_lane_of: its inverse. */
-__device__ __forceinline__ void sb_place(uint32_t lane, uint32_t &rec, uint32_t &l)
-{
-    const uint32_t p = lane & 31u, q = p >> 2; /* q: the lane's quad, 0 .. 7 */
-    const uint32_t g = (0x96u >> q) & 1u;      /* quads 1, 2, 4, 7 belong to the second group */
-    rec = 2u * (lane >> 5) + g;
-    l = g ? (p < 12 ? p - 4 : p < 20 ? p - 8 : p - 16) : (p < 4 ? p : p < 16 ? p - 8 : p - 12);
-}
-__device__ __forceinline__ uint32_t sb_lane_of(uint32_t rec, uint32_t l)
-{
-    const uint32_t p = rec & 1u ? (l < 8 ? l + 4 : l < 12 ? l + 8 : l + 16) : (l < 4 ? l : l < 8 ? l + 8 : l + 12);
-    return 32u * (rec >> 1) + p;
-}
 
 /* the passes kb .. kb + SB_BATCH - 1 of a record, one block per lane of its L */
 template <uint32_t L>
@@ -244,15 +172,10 @@ __global__ __launch_bounds__(SB_THREADS) void k_polyval_batch(SbParams P)
 {
     constexpr uint32_t LOG = L == 16 ? 4 : 6; /* fold steps; the tables are those of H^(2^s), s = 0 .. LOG */
     constexpr uint32_t NT = LOG + 1, NREC = SB_THREADS / L;
-    static_assert(L == 16 || L == 64, "a record is a quarter of a wave or a whole one");
     __shared__ __attribute__((aligned(16))) uint4 tab[NREC * NT * 16];
     const uint32_t tid = threadIdx.x;
-    uint32_t rec = tid / L, l = tid % L; /* the record of the group this lane works on, and its lane there */
-    if constexpr (L == 16) {
-        uint32_t r;
-        sb_place(tid & 63u, r, l);
-        rec = 4u * (tid >> 6) + r;
-    }
+    uint32_t rec, l; /* the record of the group this lane works on, and its lane there */
+    sb_thread<L>(tid, rec, l);
     uint4 *const T = tab + rec * NT * 16;
     const uint64_t ngroups = (P.nmsg + NREC - 1) / NREC;
     for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
@@ -273,14 +196,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_polyval_batch(SbParams P)
         }
         uint4 A = make_uint4(0, 0, 0, 0);
         if (live) {
-            const uint64_t *D = (const uint64_t *)(P.msgs + m);
-            SbRec R;
-            R.data = (gptr8)D[P.hash_out ? 1 : 0];
-            R.nbytes = D[2];
-            R.aad = (gptr8)D[3];
-            R.aad_bytes = D[4];
-            R.na = (R.aad_bytes + 15) >> 4;
-            R.nd = (R.nbytes + 15) >> 4;
+            const SbRec R = sb_record((const uint64_t *)(P.msgs + m), P.hash_out);
             const uint64_t nb = R.na + R.nd + 1;
             const uint32_t npass = (uint32_t)((nb + L - 1) / L);
             const uint64_t pad = (uint64_t)npass * L - nb; /* zero blocks in front, < L */
@@ -302,11 +218,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_polyval_batch(SbParams P)
 #pragma unroll 1
         for (uint32_t s = 0; s < LOG; ++s) {
             const uint32_t d = 1u << s;
-            /* from lane l + d of the record (a lane without one takes its own value, which nobody uses) */
-            const uint32_t ld = l + d < L ? l + d : l;
-            const int src = (int)(L == 16 ? sb_lane_of(rec & 3u, ld) : ld);
-            const uint4 B = make_uint4((uint32_t)__shfl((int)A.x, src), (uint32_t)__shfl((int)A.y, src),
-                                       (uint32_t)__shfl((int)A.z, src), (uint32_t)__shfl((int)A.w, src));
+            const uint4 B = sb_from_lane<L>(A, rec, l, d);
             A = sb_xor(sb_mul(T + s * 16, A), B);
         }
         A = sb_mul(T, A);

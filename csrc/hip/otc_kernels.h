@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_siv_batch.hip, aes_gcm_batch.hip, aes_bs.hip, chacha.hip,
+ * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_siv_batch.hip, aes_gcm_batch.hip, aes_gcm_mk_batch.hip, aes_bs.hip, chacha.hip,
  * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
@@ -271,6 +271,32 @@ hipError_t ctr_le32_batch_run(const otc_gcm_msg *msgs, const otc_aes_key *keys, 
                               const uint32_t *tile_msg, const uint64_t *tile_first, uint64_t ntiles, int nr,
                               hipStream_t st);
 inline hipError_t gcm_siv_batch_wipe(const otc_gcm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+{
+    return batch_wipe(msgs, nmsg, ok, st);
+}
+
+/* ---- aes_gcm_mk_batch.hip -------------------------------------------------- */
+/* lanes per record of the many-key batched hash kernel's two forms */
+constexpr int GMK_LANES_SHORT = 16, GMK_LANES_LONG = 64;
+/* the batched hash kernel's boundaries in hashed blocks, smallest first */
+int gcm_mk_batch_spans(uint64_t *spans, int max);
+/* bytes of the table image of nkeys keys: seven nibble tables of 256 bytes each per key */
+size_t gcm_mk_batch_table_bytes(size_t nkeys);
+/* tab (16-byte aligned) = the table images of the GHASH keys E_K(0^128) of the
+ * nkeys encryption schedules at keys (nr rounds each) */
+hipError_t gcm_mk_batch_tables(const otc_aes_key *keys, uint64_t nkeys, int nr, void *tab, hipStream_t st);
+/* s[m] (nmsg x 16, 16-byte aligned) = GHASH under the key whose image is
+ * tab[msgs[m].key] of record m's padded AAD, padded data (its `out` with
+ * hash_out, else its `in`) and length block.  lanes: GMK_LANES_SHORT or _LONG */
+hipError_t ghash_mk_batch_run(const otc_gcm_mk_msg *msgs, uint64_t nmsg, const void *tab, void *s, bool hash_out,
+                              int lanes, hipStream_t st);
+/* tags[m] = s[m] ^ E_{keys[msgs[m].key]}(j0[m]); with ok (a decryption), ok[m] =
+ * the first tag_bytes bytes equal expect[m], and the tag of a record that fails
+ * is zeroed */
+hipError_t gcm_mk_batch_final(const otc_gcm_mk_msg *msgs, const otc_aes_key *keys, const void *j0, const void *s,
+                              uint64_t nmsg, int nr, void *tags, const uint8_t *expect, int tag_bytes, uint8_t *ok,
+                              hipStream_t st);
+inline hipError_t gcm_mk_batch_wipe(const otc_gcm_mk_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
 {
     return batch_wipe(msgs, nmsg, ok, st);
 }

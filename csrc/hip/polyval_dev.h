@@ -1,8 +1,9 @@
 /*
  * polyval_dev.h -- POLYVAL's field arithmetic (RFC 8452) as the device code of
- * aes_gcm_siv.hip and aes_gcm_siv_batch.hip uses it, in plain C callable on the
- * host and on the device: csrc/cpu/gcmsiv_selftest.c and
- * csrc/cpu/gcmsiv_batch_selftest.c include this file and run the kernels'
+ * aes_gcm_siv.hip, aes_gcm_siv_batch.hip and aes_gcm_mk_batch.hip (GHASH through
+ * POLYVAL) uses it, in plain C callable on the host and on the device:
+ * csrc/cpu/gcmsiv_selftest.c, csrc/cpu/gcmsiv_batch_selftest.c and
+ * csrc/cpu/gcm_mk_batch_selftest.c include this file and run the kernels'
  * decompositions with it against aes.c.
  *
  * A block is four little-endian words as loaded, which IS POLYVAL's order:
@@ -118,6 +119,42 @@ PV_HD void pv4_dot(uint32_t z[4], const uint32_t a[4], const uint32_t (*tab)[4])
     uint32_t r[4] = {0, 0, 0, 0};
     for (int k = 0; k < 32; ++k) pv4_step(r, tab[pv4_nibble(a, k)]);
     for (int j = 0; j < 4; ++j) z[j] = r[j];
+}
+
+/* ---- what the many-key batched GCM adds (aes_gcm_mk_batch.hip) ------------------
+ * RFC 8452 appendix A: GHASH(H, X_1 .. X_n) = ByteReverse(POLYVAL(mulX_POLYVAL(
+ * ByteReverse(H)), ByteReverse(X_1), .., ByteReverse(X_n))).  So GHASH under a key
+ * per record runs on the nibble tables above: the hash key enters as gmk_key,
+ * every block enters through pv_rev, and the result leaves through pv_rev. */
+#define GMK_NTAB 7 /* a key's table image: the nibble tables of C^(2^s), s = 0 .. 6, 256 bytes each */
+
+PV_HD uint32_t pv_bswap32(uint32_t w) { return w >> 24 | (w >> 8 & 0xFF00u) | (w << 8 & 0xFF0000u) | w << 24; }
+
+/* r = the 16 bytes of x in reverse order (r and x may be the same array) */
+PV_HD void pv_rev(uint32_t r[4], const uint32_t x[4])
+{
+    const uint32_t a = pv_bswap32(x[3]), b = pv_bswap32(x[2]), c = pv_bswap32(x[1]), d = pv_bswap32(x[0]);
+    r[0] = a;
+    r[1] = b;
+    r[2] = c;
+    r[3] = d;
+}
+
+/* the POLYVAL key that stands for the GHASH key h = E_K(0^128) (four words as loaded) */
+PV_HD void gmk_key(uint32_t c[4], const uint32_t h[4])
+{
+    pv_rev(c, h);
+    pv_mulx(c);
+}
+
+/* GCM's length block [8 aad]_64 [8 n]_64, big-endian, already byte-reversed */
+PV_HD void gmk_len_block(uint32_t x[4], uint64_t aad_bytes, uint64_t nbytes)
+{
+    const uint64_t ab = aad_bytes * 8, db = nbytes * 8;
+    x[0] = (uint32_t)db;
+    x[1] = (uint32_t)(db >> 32);
+    x[2] = (uint32_t)ab;
+    x[3] = (uint32_t)(ab >> 32);
 }
 
 /* RFC 8452 section 4: derivation block i of a nonce (three words as loaded) is le32(i) || nonce */

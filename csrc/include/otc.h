@@ -444,8 +444,10 @@ int otc_aes_ctr_batch(const otc_ctr_msg *msgs, const otc_aes_key *keys, const ui
  * its own 16-byte tag: record m is SP 800-38D GCM under (key, iv[m], aad[m]).
  * The shape of TLS records, ESP / QUIC packets and sealed sectors, where
  * otc_aes_gcm's per-call cost (an allocation, 384 KiB of tables, one launch per
- * level) is all there is.  One key per batch is a decision: the positional
- * hash tables are 64 KiB per constant and cannot be held per record.
+ * level) is all there is.  One key per batch is what makes this the fast path: the
+ * positional hash tables are 64 KiB per constant and cannot be held per record.
+ * Records under many keys go to otc_aes_gcm_mk_batch below, which hashes on
+ * 256-byte tables per key.
  *
  * Limits (the planner checks them on host copies of the descriptors): data
  * 0 .. OTC_GCM_BATCH_MAX_BYTES per record, any byte count -- larger messages
@@ -773,6 +775,81 @@ int otc_aes_gcm_siv_batch(const otc_gcm_msg *msgs_dev, const uint32_t *tile_msg_
                           uint64_t ntiles, size_t nmsg, const otc_gcm_siv_key *k, int dir, const uint8_t *nonces_dev,
                           void *tags_dev, const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, int lanes,
                           void *stream);
+
+/* ---- batched AES-GCM, a key per record ---------------------------------------
+ * Many records, each under its OWN key (an index into an array of expanded
+ * encryption keys), with its own 12-byte IV, its own AAD and its own tag: record
+ * m is SP 800-38D GCM under (keys[msgs[m].key], iv[m], aad[m]) and equals
+ * otc_aes_gcm on that record alone, byte for byte.  The shape of a server's TLS
+ * records, ESP / QUIC packets and sealed sectors, which come from many
+ * connections with a key each.  otc_aes_gcm_batch stays the faster call where
+ * one key covers the batch.  GHASH runs here as POLYVAL (RFC 8452 appendix A) on
+ * nibble tables of 256 bytes, seven per key (1792 bytes), built on the device
+ * once per key and copied by every record (csrc/hip/aes_gcm_mk_batch.hip).
+ *
+ * ONE key size per batch (`nr`: 10, 12 or 14 rounds for every key): the CTR
+ * launch has one round count.  That is a decision; a caller with two key sizes
+ * makes two batches.
+ *
+ * Limits, IVs, AADs, overlap rules, tag_bytes, the verdicts on the device, the
+ * wipe of failed records and of their tag rows, and what a run may do (one
+ * linear chain of launches on `stream`, no allocation, no host synchronisation,
+ * capturable in a graph) are exactly otc_aes_gcm_batch's:
+ *   encrypt: prep -> CTR batch -> batched GHASH over out -> finisher (tags)
+ *   decrypt: prep -> batched GHASH over in -> finisher (tags, verdicts)
+ *            -> CTR batch -> wipe
+ * The finisher forms tag = GHASH ^ E_{K_m}(J0_m) with the schedule read from
+ * keys_dev.  otc_last_impl: OTC_IMPL_TTABLE.
+ *
+ * keys_dev (nkeys otc_aes_key, 256 bytes each) and the table image hold
+ * KEY MATERIAL: the schedules and what derives from the hash keys E_K(0^128).
+ * Clearing them when the batch is done with is the caller's job. */
+typedef struct {
+    uint64_t in;        /* device addresses */
+    uint64_t out;
+    uint64_t nbytes;
+    uint64_t aad;
+    uint64_t aad_bytes; /* otc_chacha_msg's columns, on purpose: the wipe kernel serves this one too */
+    uint64_t key;       /* index into keys_dev and into the table image */
+} otc_gcm_mk_msg;
+
+/* Host planner over HOST copies of the descriptors: otc_gcm_batch_plan's checks
+ * and key < nkeys; fills the CTR half's descriptors (key index set, counters left
+ * zero: prep writes them), tile map and tile_first -- any of the three may be
+ * NULL to only count.  Returns the number of tiles (records of 0 bytes have
+ * none), or OTC_ERR_ARG with a message "gcm_mk_batch: record M: ...".  Needs no
+ * device. */
+int64_t otc_gcm_mk_batch_plan(const otc_gcm_mk_msg *msgs, size_t nmsg, size_t nkeys, int tile_blocks,
+                              otc_ctr_msg *ctr_msgs, uint32_t *tile_msg, uint64_t *tile_first);
+/* bytes of the table image of nkeys keys (1792 each), 16-byte aligned device memory */
+size_t otc_gcm_mk_batch_table_bytes(size_t nkeys);
+/* Builds the table image of the nkeys schedules at keys_dev (device memory,
+ * 8-byte aligned, every one an ENCRYPTION schedule with nr rounds) into tab_dev:
+ * one launch on `stream`; once per plan, and again when the keys change. */
+int otc_gcm_mk_batch_tables(const otc_aes_key *keys_dev, size_t nkeys, int nr, void *tab_dev, void *stream);
+/* the caller-owned workspace of a run: J0[] and the hashes, 32 bytes per record, 16-byte aligned */
+size_t otc_gcm_mk_batch_ws_bytes(size_t nmsg);
+/* How many lanes hash one record: 16 (four records per wave) or 64 (one wave per
+ * record).  Both compute the same; the choice is speed only.  From HOST copies
+ * of the descriptors (what the rule rests on: aead.cpp). */
+int otc_gcm_mk_batch_lanes(const otc_gcm_mk_msg *msgs, size_t nmsg);
+/* The batched hash kernel's own boundaries in HASHED BLOCKS (AAD, data and
+ * length block together), smallest first: 16, 64, 256, as otc_gcm_batch_spans. */
+int otc_gcm_mk_batch_spans(uint64_t *spans, int max);
+/* The hash by itself: s_dev[m] (nmsg x 16, 16-byte aligned) = GHASH, under the
+ * hash key of key msgs[m].key, of record m's AAD, `in` data and length block.
+ * tab_dev: the image from otc_gcm_mk_batch_tables.  lanes: 16 or 64 (0: 64). */
+int otc_ghash_mk_batch(const otc_gcm_mk_msg *msgs_dev, size_t nmsg, const void *tab_dev, void *s_dev, int lanes,
+                       void *stream);
+/* The arguments of otc_aes_gcm_batch, with keys_dev / nkeys / nr in place of k /
+ * key_dev: the schedule array serves the CTR kernel and the finisher, tab_dev is
+ * its table image.  nmsg == 0 launches nothing.  Every bad argument is
+ * OTC_ERR_ARG before any HIP call. */
+int otc_aes_gcm_mk_batch(const otc_gcm_mk_msg *msgs_dev, otc_ctr_msg *ctr_msgs_dev, const uint32_t *tile_msg_dev,
+                         const uint64_t *tile_first_dev, uint64_t ntiles, int tile_blocks, size_t nmsg,
+                         const otc_aes_key *keys_dev, size_t nkeys, int nr, const void *tab_dev, int dir,
+                         const uint8_t *ivs_dev, void *tags_dev, const uint8_t *expect_dev, int tag_bytes,
+                         uint8_t *ok_dev, void *ws_dev, int lanes, void *stream);
 
 /* out = a ^ b (the device arc4_crypt combiner). */
 int otc_xor(const void *a, const void *b, void *out, size_t nbytes, void *stream);

@@ -273,6 +273,15 @@ def _declare_gpu(lib):
         "otc_ghash_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
         "otc_aes_gcm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u64, c_int, c_sz, P(OtcGcmKey), c_vp, c_vp, c_int,
                                       c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
+        "otc_gcm_mk_batch_spans": (c_int, [P(c_u64), c_int]),
+        "otc_gcm_mk_batch_table_bytes": (c_sz, [c_sz]),
+        "otc_gcm_mk_batch_ws_bytes": (c_sz, [c_sz]),
+        "otc_gcm_mk_batch_tables": (c_int, [c_vp, c_sz, c_int, c_vp, c_vp]),
+        "otc_gcm_mk_batch_plan": (ctypes.c_int64, [c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp]),
+        "otc_gcm_mk_batch_lanes": (c_int, [c_vp, c_sz]),
+        "otc_ghash_mk_batch": (c_int, [c_vp, c_sz, c_vp, c_vp, c_int, c_vp]),
+        "otc_aes_gcm_mk_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u64, c_int, c_sz, c_vp, c_sz, c_int, c_vp, c_int,
+                                         c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
         "otc_gcm_siv_key_init": (c_int, [P(OtcGcmSivKey), c_u8p, c_int]),
         "otc_aes_gcm_siv": (c_int, [c_vp, c_vp, c_sz, P(OtcGcmSivKey), c_int, c_u8p, c_u8p, c_sz, c_vp, c_vp, c_vp]),
         "otc_aes_ctr_le32": (c_int, [c_vp, c_vp, c_sz, K, c_vp, c_vp]),

@@ -218,6 +218,21 @@ def gcm(key: bytes, iv: bytes, data: bytes, aad: bytes = b"", decrypt: bool = Fa
     return bytes(out)[: len(data)], bytes(tag)
 
 
+def gcm_mk_batch(keys, key_index, ivs, datas, aads=None, decrypt: bool = False):
+    """The oracle of the batched AES-GCM with a key per record: a loop over
+    ``gcm``.  Record ``m`` is SP 800-38D GCM under ``(keys[key_index[m]],
+    ivs[m], aads[m])`` (``key_index`` None: key m for record m): a list of
+    ``(out, tag)`` with the COMPUTED 16-byte tags in both directions."""
+    keys, ivs, datas = [bytes(k) for k in keys], [bytes(v) for v in ivs], [bytes(d) for d in datas]
+    aads = [b""] * len(datas) if aads is None else [bytes(a) for a in aads]
+    kidx = list(range(len(datas))) if key_index is None else [int(k) for k in key_index]
+    if len(ivs) != len(datas) or len(aads) != len(datas) or len(kidx) != len(datas):
+        raise ValueError("one key index, one IV and one AAD per record")
+    if any(k < 0 or k >= len(keys) for k in kidx):
+        raise ValueError("key_index out of range")
+    return [gcm(keys[k], v, d, a, decrypt=decrypt) for k, v, d, a in zip(kidx, ivs, datas, aads)]
+
+
 def gcm_auth_decrypt(key: bytes, iv: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
     """Authenticated decryption: compares 4..16 tag bytes in constant time and
     raises GcmTagError (the C side zeroes its output) on a mismatch."""

@@ -12,6 +12,7 @@ from . import ocb_ops  # AES-OCB3: its names are not in __all__ yet either (docs
 from . import ocb_batch_ops  # batched AES-OCB3: the same arrangement (docs/API.md)
 from . import gcm_siv_ops  # AES-GCM-SIV and POLYVAL: the same arrangement (docs/API.md)
 from . import gcm_siv_batch_ops  # batched AES-GCM-SIV: the same arrangement (docs/API.md)
+from . import gcm_mk_batch_ops  # batched AES-GCM with a key per record: the same arrangement (docs/API.md)
 from .gcm_ops import GcmTagError, gcm_decrypt, gcm_encrypt, ghash, ghash_spans
 from .keys import expand_key
 from .stream_ops import checksum, clock_ghz, clock_probe, fill_random_, rc4_crypt_batch, rc4_multi, rc4_states, xor
