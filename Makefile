@@ -37,14 +37,14 @@ OBJ    := build/obj
 
 CPU_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/rc4.c csrc/cpu/aesni.c csrc/cpu/numa.c csrc/cpu/rccl_plan.c csrc/cpu/chacha.c
 CPU_OBJ := $(patsubst csrc/cpu/%.c,$(OBJ)/cpu/%.o,$(CPU_SRC)) $(OBJ)/cpu/bs_selftest.o
-HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_ocb.hip csrc/hip/aes_ocb_batch.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_siv.hip csrc/hip/aes_gcm_siv_batch.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_gcm_mk_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/chacha_batch.hip csrc/hip/stream_ops.hip
+HIP_SRC := csrc/hip/aes_tt.hip csrc/hip/aes_xts.hip csrc/hip/aes_ocb.hip csrc/hip/aes_ocb_batch.hip csrc/hip/aes_ccm_batch.hip csrc/hip/aes_gcm.hip csrc/hip/aes_gcm_siv.hip csrc/hip/aes_gcm_siv_batch.hip csrc/hip/aes_gcm_batch.hip csrc/hip/aes_gcm_mk_batch.hip csrc/hip/aes_bs.hip csrc/hip/chacha.hip csrc/hip/chacha_batch.hip csrc/hip/stream_ops.hip
 HIP_OBJ := $(patsubst csrc/hip/%.hip,$(OBJ)/hip/%.o,$(HIP_SRC)) $(OBJ)/hip/engine.o $(OBJ)/hip/aead.o $(OBJ)/hip/runtime.o $(OBJ)/hip/split.o $(OBJ)/hip/pipeline.o
 
 BINS := bin/test bin/aes_test bin/aes_ecb_e bin/aes_ecb_d bin/otbench bin/bc_test
 
 .PHONY: all cpu clean
-all: $(LIBDIR)/libotc.so $(LIBDIR)/libotc_cpu.so $(BINS) bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest ref-o0
-cpu: $(LIBDIR)/libotc_cpu.so bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest ref-o0
+all: $(LIBDIR)/libotc.so $(LIBDIR)/libotc_cpu.so $(BINS) bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/ccm_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest ref-o0
+cpu: $(LIBDIR)/libotc_cpu.so bin/test_cpu bin/aes_test_cpu bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/ccm_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest ref-o0
 
 $(OBJ)/cpu/aesni.o: csrc/cpu/aesni.c csrc/include/aesni.h
 	@mkdir -p $(dir $@)
@@ -134,6 +134,14 @@ bin/ocb_batch_selftest: csrc/cpu/ocb_batch_selftest.c csrc/hip/ocb_dev.h $(OBJ)/
 	@mkdir -p bin
 	$(CC) -O2 -g -std=gnu99 -Wall -Wextra -Wno-unknown-pragmas $(INC) $< $(OBJ)/cpu/aes.o -o $@ -lpthread $(SANLD)
 
+# the batched CCM kernel's decomposition on the host, with the kernel's own block
+# formatting (csrc/hip/ccm_dev.h: B0 / A_i, the encoded AAD's blocks, the pipelined
+# decryption order, the bursts, the tail mask, the order), against aes.c
+# (tests/test_ccm_batch_selftest_cpu.py also builds it with -fsanitize=address,undefined)
+bin/ccm_batch_selftest: csrc/cpu/ccm_batch_selftest.c csrc/hip/ccm_dev.h $(OBJ)/cpu/aes.o
+	@mkdir -p bin
+	$(CC) -O2 -g -std=gnu99 -Wall -Wextra $(INC) $< $(OBJ)/cpu/aes.o -o $@ -lpthread $(SANLD)
+
 # the GCM-SIV oracle's vectors, counter wrap and tamper checks, and the POLYVAL
 # kernels' decomposition on the host with the kernels' own field arithmetic
 # (csrc/hip/polyval_dev.h), against aes.c (tests/test_gcm_siv_selftest_cpu.py also
@@ -203,7 +211,7 @@ bin/aes_test_o0: csrc/cli/aes_test.c $(O0_OBJ)
 	$(CXX) -O0 -g $(INC) -x c -std=gnu99 $< -x none $(O0_OBJ) -o $@ -lpthread
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
+	rm -rf build $(LIBDIR)/*.so $(BINS) bin/otbench_hostsim bin/poly_batch_selftest bin/ocb_selftest bin/ocb_batch_selftest bin/ccm_batch_selftest bin/gcmsiv_selftest bin/gcmsiv_batch_selftest bin/gcm_mk_batch_selftest bin/test_cpu bin/aes_test_cpu bin/test_o0 bin/aes_test_o0
 
 # Host sanitizers over the threaded CPU paths (also tests/test_sanitizers_cpu.py)
 SAN_SRC := csrc/cpu/aes.c csrc/cpu/arc4.c csrc/cpu/chacha.c csrc/cli/san_driver.c

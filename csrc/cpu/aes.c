@@ -1155,6 +1155,92 @@ int aes_ocb_auth_decrypt(const aes_ocb_context *ctx, size_t length, const unsign
 }
 
 /* ---------------------------------------------------------------------------
+ * AES-CCM (NIST SP 800-38C, RFC 3610), written from the two documents: the tag
+ * is a CBC-MAC over B0 || encoded AAD || data (each zero-padded to a block), the
+ * data runs in counter mode on A_1 .., the tag is MSB_M(T ^ E(A_0)).
+ * ------------------------------------------------------------------------- */
+static int ccm_lengths_ok(size_t length, size_t nonce_len, size_t aad_len, size_t tag_len)
+{
+    if (nonce_len < 7 || nonce_len > 13) return 0;
+    if (tag_len < 4 || tag_len > 16 || (tag_len & 1)) return 0;
+    const unsigned L = 15u - (unsigned)nonce_len; /* 2 .. 8 */
+    if (L < 8 && ((uint64_t)length >> (8 * L))) return 0;
+    if ((uint64_t)aad_len >> 32) return 0; /* the 6-byte encoding; the 10-byte one is not built */
+    return 1;
+}
+
+/* flags || N || [v]_L */
+static void ccm_block(unsigned char b[16], unsigned flags, const unsigned char *nonce, size_t nonce_len, uint64_t v)
+{
+    b[0] = (unsigned char)flags;
+    memcpy(b + 1, nonce, nonce_len);
+    for (size_t i = 15; i > nonce_len; --i, v >>= 8) b[i] = (unsigned char)v;
+}
+
+int aes_crypt_ccm(const aes_context *ctx, int mode, size_t length, const unsigned char *nonce, size_t nonce_len,
+                  const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                  unsigned char tag[16], size_t tag_len)
+{
+    if (!ccm_lengths_ok(length, nonce_len, aad_len, tag_len)) return POLARSSL_ERR_AES_INVALID_INPUT_LENGTH;
+    ensure_tables();
+    const unsigned L = 15u - (unsigned)nonce_len;
+    unsigned char x[16], a[16], s[16], s0[16];
+    ccm_block(x, (aad_len ? 64u : 0u) + 8u * (((unsigned)tag_len - 2u) / 2u) + (L - 1u), nonce, nonce_len, length);
+    encrypt_block(ctx, x, x);
+    if (aad_len) {
+        /* the length's encoding, the AAD, zeros up to a block */
+        unsigned char hdr[6];
+        size_t h;
+        if (aad_len < 0xFF00) {
+            hdr[0] = (unsigned char)(aad_len >> 8), hdr[1] = (unsigned char)aad_len, h = 2;
+        } else {
+            hdr[0] = 0xFF, hdr[1] = 0xFE, h = 6;
+            for (int i = 0; i < 4; ++i) hdr[2 + i] = (unsigned char)((uint64_t)aad_len >> (24 - 8 * i));
+        }
+        size_t fill = 0;
+        for (size_t i = 0; i < h; ++i) x[fill++] ^= hdr[i];
+        for (size_t i = 0; i < aad_len; ++i) {
+            x[fill++] ^= aad[i];
+            if (fill == 16) encrypt_block(ctx, x, x), fill = 0;
+        }
+        if (fill) encrypt_block(ctx, x, x);
+    }
+    ccm_block(a, L - 1u, nonce, nonce_len, 0);
+    encrypt_block(ctx, a, s0);
+    uint64_t ctr = 0;
+    for (size_t at = 0; at < length; at += 16) {
+        const size_t n = length - at < 16 ? length - at : 16;
+        ccm_block(a, L - 1u, nonce, nonce_len, ++ctr);
+        encrypt_block(ctx, a, s);
+        for (size_t i = 0; i < n; ++i) {
+            const unsigned char c = (unsigned char)(input[at + i] ^ s[i]);
+            x[i] ^= mode == AES_ENCRYPT ? input[at + i] : c; /* the plaintext, either way */
+            output[at + i] = c;
+        }
+        encrypt_block(ctx, x, x);
+    }
+    memset(tag, 0, 16);
+    for (size_t i = 0; i < tag_len; ++i) tag[i] = (unsigned char)(x[i] ^ s0[i]);
+    return 0;
+}
+
+int aes_ccm_auth_decrypt(const aes_context *ctx, size_t length, const unsigned char *nonce, size_t nonce_len,
+                         const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
+                         const unsigned char *input, unsigned char *output)
+{
+    unsigned char t[16];
+    const int r = aes_crypt_ccm(ctx, AES_DECRYPT, length, nonce, nonce_len, aad, aad_len, input, output, t, tag_len);
+    if (r) return r;
+    unsigned diff = 0; /* every byte compared, whatever the earlier ones gave */
+    for (size_t i = 0; i < tag_len; ++i) diff |= (unsigned)(t[i] ^ tag[i]);
+    if (diff) {
+        if (length) memset(output, 0, length);
+        return POLARSSL_ERR_CCM_AUTH_FAILED;
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------
  * Self test: FIPS-197 appendix C, SP 800-38A F.1/F.2/F.3/F.5, RFC 3686 #1-#3,
  * and the 10,000-iteration Monte-Carlo ECB/CBC chains of the NIST
  * rijndael-vals set that the reference's self-test runs

@@ -5,7 +5,8 @@
  * ChaCha20, Poly1305 and ChaCha20-Poly1305 (chacha.hip), batched GCM
  * (aes_gcm_batch.hip and the batched CTR kernel), batched
  * ChaCha20-Poly1305 (chacha_batch.hip), batched OCB3
- * (aes_ocb_batch.hip), batched GCM-SIV (aes_gcm_siv_batch.hip) and batched GCM
+ * (aes_ocb_batch.hip), batched CCM (aes_ccm_batch.hip), batched GCM-SIV
+ * (aes_gcm_siv_batch.hip) and batched GCM
  * with a key per record (aes_gcm_mk_batch.hip): the argument checks, what an
  * op computes on the host (J0, the AAD's hash, the one-time key, the length
  * blocks) and the order of its launches.
@@ -23,6 +24,7 @@
 #include "otc.h"
 #include "otc_device.h"
 #include "engine_internal.h"
+#include "ccm_dev.h"
 
 using namespace otc_rt;
 
@@ -816,6 +818,78 @@ extern "C" int otc_aes_ocb_batch(const otc_ocb_msg *msgs_dev, const uint32_t *ti
     if (e != hipSuccess) return hip_fail(e, "ocb_batch finish launch");
     if (!enc && (e = otc_impl::ocb_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
         return hip_fail(e, "ocb_batch wipe launch");
+    return OTC_OK;
+}
+
+/* ---- batched AES-CCM: many records, one key, one record per lane ---------------- */
+extern "C" int otc_ccm_batch_spans(uint64_t *spans, int max) { return otc_impl::ccm_batch_spans(spans, spans ? max : 0); }
+
+extern "C" size_t otc_ccm_batch_ws_bytes(size_t) { return 0; /* the AAD is chained in the records' kernel */ }
+
+static bool ccm_tag_len_ok(int t) { return t >= 4 && t <= 16 && !(t & 1); }
+
+extern "C" int otc_ccm_batch_plan(const otc_ccm_msg *msgs, size_t nmsg, int nonce_len, uint32_t *order)
+{
+    if (nonce_len < 7 || nonce_len > 13) return set_err(OTC_ERR_ARG, "ccm_batch: a nonce has 7 to 13 bytes");
+    if (nmsg == 0) return OTC_OK;
+    if (!msgs) return set_err(OTC_ERR_ARG, "ccm_batch: null descriptors");
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "ccm_batch: more than 2^32 - 1 records");
+    auto bad = [](size_t m, const char *what) {
+        return set_err(OTC_ERR_ARG, "ccm_batch: record " + std::to_string(m) + ": " + what);
+    };
+    /* the length field has L = 15 - nonce_len bytes (2 .. 8); the cap is below 2^24 */
+    const int L = 15 - nonce_len;
+    const uint64_t field = L >= 3 ? (uint64_t)OTC_CCM_BATCH_MAX_BYTES + 1 : (uint64_t)1 << (8 * L);
+    for (size_t m = 0; m < nmsg; ++m) {
+        if (const char *f = batch_record_fault(msgs[m], OTC_CCM_BATCH_MAX_BYTES, OTC_CCM_BATCH_MAX_AAD,
+                                               "more than 1 MiB of data"))
+            return bad(m, f);
+        if (msgs[m].nbytes >= field) return bad(m, "its length does not fit the length field of this nonce length");
+    }
+    if (int r = batch_overlaps(msgs, nmsg, bad)) return r;
+    static_assert(sizeof(otc_ccm_msg) % 8 == 0, "ccm_order_fill strides in 64-bit words");
+    if (order && ccm_order_fill(order, &msgs[0].nbytes, sizeof(otc_ccm_msg) / 8, nmsg))
+        return set_err(OTC_ERR_NOMEM, "ccm_batch: no memory for the order's sort");
+    return OTC_OK;
+}
+
+extern "C" int otc_aes_ccm_batch(const otc_ccm_msg *msgs_dev, const uint32_t *order_dev, size_t nmsg,
+                                 const otc_aes_key *key, int dir, const uint8_t *nonces_dev, int nonce_len,
+                                 void *tags_dev, int tag_len, const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev,
+                                 void *stream)
+{
+    Range rg("otc_aes_ccm_batch");
+    (void)ws_dev; /* otc_ccm_batch_ws_bytes is 0 */
+    if (!key) return set_err(OTC_ERR_ARG, "null key");
+    if (int r = check_key(key, OTC_DIR_ENCRYPT)) return r;
+    if (dir != OTC_DIR_ENCRYPT && dir != OTC_DIR_DECRYPT) return set_err(OTC_ERR_ARG, "bad direction");
+    if (nonce_len < 7 || nonce_len > 13) return set_err(OTC_ERR_ARG, "ccm_batch: a nonce has 7 to 13 bytes");
+    if (!ccm_tag_len_ok(tag_len)) return set_err(OTC_ERR_ARG, "ccm_batch: a tag has 4, 6, 8, 10, 12, 14 or 16 bytes");
+    if (nmsg == 0) return OTC_OK;
+    if (nmsg > 0xFFFFFFFFull) return set_err(OTC_ERR_ARG, "ccm_batch: more than 2^32 - 1 records");
+    if (!msgs_dev || !order_dev || !tags_dev) return set_err(OTC_ERR_ARG, "ccm_batch: null array");
+    if ((uintptr_t)msgs_dev & 7u) return set_err(OTC_ERR_ARG, "ccm_batch: misaligned descriptor array");
+    if ((uintptr_t)order_dev & 3u) return set_err(OTC_ERR_ARG, "ccm_batch: misaligned order array");
+    if (dir == OTC_DIR_DECRYPT && (!expect_dev || !ok_dev))
+        return set_err(OTC_ERR_ARG, "ccm_batch: decryption needs the expected tags and the verdict array");
+    if (dir == OTC_DIR_DECRYPT) {
+        /* the expected tags are compared with what this call computes: never its own output */
+        const uintptr_t e0 = (uintptr_t)expect_dev, e1 = e0 + nmsg * (size_t)tag_len;
+        const uintptr_t t0 = (uintptr_t)tags_dev, v0 = (uintptr_t)ok_dev;
+        if ((e0 < t0 + nmsg * (size_t)tag_len && t0 < e1) || (e0 < v0 + nmsg && v0 < e1))
+            return set_err(OTC_ERR_ARG, "ccm_batch: the expected tags overlap the computed tags or the verdicts");
+    }
+    if (!nonces_dev) return set_err(OTC_ERR_ARG, "ccm_batch: null nonces");
+    hipStream_t st = (hipStream_t)stream;
+    set_last_impl(OTC_IMPL_TTABLE);
+    const bool enc = dir == OTC_DIR_ENCRYPT;
+
+    hipError_t e = otc_impl::ccm_batch_run(msgs_dev, order_dev, nmsg, *key, !enc, nonces_dev, nonce_len,
+                                           (uint8_t *)tags_dev, tag_len, enc ? nullptr : expect_dev,
+                                           enc ? nullptr : ok_dev, st);
+    if (e != hipSuccess) return hip_fail(e, "ccm_batch records launch");
+    if (!enc && (e = otc_impl::ccm_batch_wipe(msgs_dev, nmsg, ok_dev, st)) != hipSuccess)
+        return hip_fail(e, "ccm_batch wipe launch");
     return OTC_OK;
 }
 

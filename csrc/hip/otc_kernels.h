@@ -1,6 +1,6 @@
 /*
  * otc_kernels.h -- the host entry points of the kernel files (aes_tt.hip,
- * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_siv_batch.hip, aes_gcm_batch.hip, aes_gcm_mk_batch.hip, aes_bs.hip, chacha.hip,
+ * aes_xts.hip, aes_ocb.hip, aes_ocb_batch.hip, aes_ccm_batch.hip, aes_gcm.hip, aes_gcm_siv.hip, aes_gcm_siv_batch.hip, aes_gcm_batch.hip, aes_gcm_mk_batch.hip, aes_bs.hip, chacha.hip,
  * chacha_batch.hip, stream_ops.hip), declared once: included by their callers (engine.cpp,
  * aead.cpp, split.cpp) and by the files that define them, so every
  * definition is checked against the declaration its callers see.  Not part
@@ -241,6 +241,20 @@ hipError_t ocb_batch_bulk(const otc_ocb_msg *msgs, uint64_t nmsg, const uint32_t
 hipError_t ocb_batch_finish(const otc_ocb_msg *msgs, uint64_t nmsg, const otc_ocb_key &k, void *ws, void *tags,
                             const uint8_t *expect, uint8_t *ok, hipStream_t st);
 inline hipError_t ocb_batch_wipe(const otc_ocb_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
+{
+    return batch_wipe(msgs, nmsg, ok, st);
+}
+
+/* ---- aes_ccm_batch.hip ---------------------------------------------------- */
+/* the kernel's boundaries, smallest first (otc.h otc_ccm_batch_spans); returns how many there are */
+int ccm_batch_spans(uint64_t *spans, int max);
+/* every record in one launch, lane t on record order[t]: out, tags[m] (tag_len
+ * bytes each, any alignment); with dec, ok[m] = the tag equals expect[m], and the
+ * tag of a record that fails is zeroed.  K: the encryption schedule, either way */
+hipError_t ccm_batch_run(const otc_ccm_msg *msgs, const uint32_t *order, uint64_t nmsg, const otc_aes_key &K, bool dec,
+                         const uint8_t *nonces, int nonce_len, uint8_t *tags, int tag_len, const uint8_t *expect,
+                         uint8_t *ok, hipStream_t st);
+inline hipError_t ccm_batch_wipe(const otc_ccm_msg *msgs, uint64_t nmsg, const uint8_t *ok, hipStream_t st)
 {
     return batch_wipe(msgs, nmsg, ok, st);
 }

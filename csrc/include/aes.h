@@ -208,6 +208,23 @@ int aes_ocb_auth_decrypt(const aes_ocb_context *ctx, size_t length, const unsign
                          const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
                          const unsigned char *input, unsigned char *output);
 
+/* AES-CCM (NIST SP 800-38C, RFC 3610), written from the two documents (the
+ * reference has no authenticated mode).  nonce_len 7..13 bytes (L = 15 -
+ * nonce_len), tag_len one of 4, 6, .., 16 bytes, length < 2^(8L), aad_len <
+ * 2^32 (the 2- and the 6-byte length encodings).  ctx: the ENCRYPTION schedule,
+ * in both directions.  May run in place. */
+#define POLARSSL_ERR_CCM_AUTH_FAILED -0x0016
+/* mode AES_ENCRYPT / AES_DECRYPT; tag: the COMPUTED tag in both directions,
+ * its first tag_len bytes, the rest of the 16 zero */
+int aes_crypt_ccm(const aes_context *ctx, int mode, size_t length, const unsigned char *nonce, size_t nonce_len,
+                  const unsigned char *aad, size_t aad_len, const unsigned char *input, unsigned char *output,
+                  unsigned char tag[16], size_t tag_len);
+/* decrypts and compares the tag_len tag bytes in constant time; on a mismatch
+ * output is zeroed and POLARSSL_ERR_CCM_AUTH_FAILED returned */
+int aes_ccm_auth_decrypt(const aes_context *ctx, size_t length, const unsigned char *nonce, size_t nonce_len,
+                         const unsigned char *aad, size_t aad_len, const unsigned char *tag, size_t tag_len,
+                         const unsigned char *input, unsigned char *output);
+
 /* Monte-Carlo known-answer chains of the reference self-test
  * (aes-modes/aes.c:1084-1200): 10,000 chained operations from an all-zero
  * key / block / IV.  aes_monte_carlo writes the final block (CBC-enc: the last

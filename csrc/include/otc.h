@@ -689,6 +689,78 @@ int otc_aes_ocb_batch(const otc_ocb_msg *msgs_dev, const uint32_t *tile_msg_dev,
                       uint64_t ntiles, size_t nmsg, const otc_ocb_key *k, int dir, const uint8_t *nonces_dev,
                       void *tags_dev, const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, void *stream);
 
+/* ---- batched AES-CCM ------------------------------------------------------------
+ * Many records under ONE key (an otc_aes_key ENCRYPTION schedule, in both
+ * directions: CCM never runs the inverse cipher), each with its own nonce, its
+ * own AAD and its own tag: record m is NIST SP 800-38C / RFC 3610 AES-CCM under
+ * (key, nonces[m], aad[m]).  The nonce length (7 .. 13 bytes; L = 15 -
+ * nonce_len) and the tag length (4, 6, .., 16 bytes) are the BATCH's.  CCM's
+ * tag is a CBC-MAC, one serial chain per record, so the kernel runs one record
+ * per lane, the chain and the counter mode as two blocks in flight, and reads
+ * the data once (csrc/hip/aes_ccm_batch.hip).  There is no single-message
+ * kernel: one message is one chain on one lane, a batch of one.
+ *
+ * Limits (the planner checks them on host copies of the descriptors): data
+ * 0 .. OTC_CCM_BATCH_MAX_BYTES per record and below 2^(8 L), any byte count;
+ * AAD 0 .. OTC_CCM_BATCH_MAX_AAD, device memory, any alignment (both encodings
+ * of its length occur: 2 bytes below 0xFF00, 6 from there); data buffers
+ * 16-byte aligned; in == out allowed per record; distinct records must not
+ * overlap, no input may overlap another record's output, and no AAD may overlap
+ * any record's output.  A record of 0 bytes is valid, with AAD or without.
+ *
+ * The nonces are DEVICE data supplied to every run (n x nonce_len bytes): a
+ * replayed batch must bring new nonces, and nonce uniqueness under the key is
+ * the caller's duty.  A run is one linear chain of launches on `stream` -- no
+ * allocation, no host synchronisation, no second stream -- so it can be
+ * captured in a graph:
+ *   encrypt: records (out, tags)
+ *   decrypt: records (out, tags, verdicts) -> wipe
+ * The MAC is over the plaintext, so a decryption decrypts before it can judge:
+ * every computed tag is compared on the device with expect_dev (n x tag_len; OR
+ * of the XORs, no early exit), ok_dev[m] becomes 1 or 0, and the output of every
+ * record with ok_dev[m] == 0 is zeroed (in place: the ciphertext with it), and
+ * so is its row of tags_dev.  expect_dev must not overlap tags_dev or ok_dev
+ * (rejected).  otc_last_impl: OTC_IMPL_TTABLE. */
+#define OTC_CCM_BATCH_MAX_BYTES (1u << 20)
+#define OTC_CCM_BATCH_MAX_AAD (1u << 16)
+typedef struct {
+    uint64_t in;        /* device addresses */
+    uint64_t out;
+    uint64_t nbytes;
+    uint64_t aad;
+    uint64_t aad_bytes; /* the five columns of otc_gcm_msg, on purpose: the wipe kernel serves this one too */
+    uint64_t reserved;
+} otc_ccm_msg;
+
+/* Host planner over HOST copies of the descriptors: checks nonce_len, the caps
+ * (nbytes <= OTC_CCM_BATCH_MAX_BYTES and nbytes < 2^(8 (15 - nonce_len)): with a
+ * 13-byte nonce 65535 bytes pass and 65536 do not), null pointers, the
+ * alignment, partial overlap of a record's in and out, overlap between records
+ * and of an AAD with any output; fills order[nmsg] (may be NULL to only check):
+ * the records sorted by their data's block count, longest first, records of one
+ * count in their own order -- lane t of the kernel takes record order[t], so the
+ * lanes of a wave end together.  Any permutation of 0 .. nmsg - 1 is a valid
+ * order.  Returns OTC_OK, or OTC_ERR_ARG with a message that names the record.
+ * Needs no device. */
+int otc_ccm_batch_plan(const otc_ccm_msg *msgs, size_t nmsg, int nonce_len, uint32_t *order);
+/* the caller-owned workspace of a run: none today (the AAD is chained in the
+ * records' kernel), so 0, and ws_dev may then be NULL */
+size_t otc_ccm_batch_ws_bytes(size_t nmsg);
+/* The kernel's boundaries, smallest first: a block and a lane's burst (8
+ * blocks) in BYTES; a wave, a workgroup and the full grid's first step -- past
+ * it a wave takes a second record per lane -- in RECORDS.  Writes up to max of
+ * them; returns the count. */
+int otc_ccm_batch_spans(uint64_t *spans, int max);
+/* order_dev: nmsg x uint32, a permutation (otc_ccm_batch_plan).  nonces_dev:
+ * nmsg x nonce_len bytes, any alignment.  tags_dev: nmsg x tag_len bytes, any
+ * alignment, the COMPUTED tags in both directions (decryption: zero for the
+ * records that fail); expect_dev (nmsg x tag_len) / ok_dev: decryption only.
+ * The round keys travel by value.  nmsg == 0 launches nothing.  Every bad
+ * argument is OTC_ERR_ARG before any HIP call. */
+int otc_aes_ccm_batch(const otc_ccm_msg *msgs_dev, const uint32_t *order_dev, size_t nmsg, const otc_aes_key *key,
+                      int dir, const uint8_t *nonces_dev, int nonce_len, void *tags_dev, int tag_len,
+                      const uint8_t *expect_dev, uint8_t *ok_dev, void *ws_dev, void *stream);
+
 /* ---- batched AES-GCM-SIV ------------------------------------------------------
  * Many records under ONE key-generating key (otc_gcm_siv_key, 128 or 256 bits),
  * each with its own 12-byte nonce, its own AAD and its own 16-byte tag: record m

@@ -201,6 +201,8 @@ def _declare_cpu(lib):
         "aes_crypt_ocb_blocks": (c_int, [P(AesOcbContext), c_int, c_u8p, c_u64, c_u64, c_u8p, c_u8p, c_u8p]),
         "aes_crypt_ocb": (c_int, [P(AesOcbContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_sz]),
         "aes_ocb_auth_decrypt": (c_int, [P(AesOcbContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
+        "aes_crypt_ccm": (c_int, [P(AesContext), c_int, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_sz]),
+        "aes_ccm_auth_decrypt": (c_int, [P(AesContext), c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p]),
         "chacha20_block": (None, [c_u8p, c_u8p, ctypes.c_uint32, c_u8p]),
         "chacha20_crypt": (c_int, [c_u8p, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_sz]),
         "poly1305_mac": (None, [c_u8p, c_u8p, c_sz, c_u8p]),
@@ -304,6 +306,11 @@ def _declare_gpu(lib):
         "otc_ocb_batch_ws_bytes": (c_sz, [c_sz]),
         "otc_ocb_batch_spans": (c_int, [P(c_u64), c_int]),
         "otc_aes_ocb_batch": (c_int, [c_vp, c_vp, c_vp, c_u64, c_sz, P(OtcOcbKey), c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp]),
+        "otc_ccm_batch_plan": (c_int, [c_vp, c_sz, c_int, c_vp]),
+        "otc_ccm_batch_ws_bytes": (c_sz, [c_sz]),
+        "otc_ccm_batch_spans": (c_int, [P(c_u64), c_int]),
+        "otc_aes_ccm_batch": (c_int, [c_vp, c_vp, c_sz, P(OtcAesKey), c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp,
                                       c_vp]),
         "otc_chacha20": (c_int, [c_vp, c_vp, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_vp]),
         "otc_poly1305": (c_int, [c_vp, c_sz, c_u8p, c_vp, c_vp]),

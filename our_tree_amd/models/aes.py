@@ -157,6 +157,20 @@ class AES:
         of every record whose tag does not match is zeroed."""
         return ops.ocb_batch_ops.ocb_decrypt_batch(xs, self._key, nonces, tags, aads=aads, outs=outs)
 
+    # ---- authenticated: batched AES-CCM (SP 800-38C, RFC 3610), one record per lane ----
+    def ccm_encrypt_batch(self, xs, nonces, aads=None, outs=None, tag_bytes: int = 16):
+        """Many GPU records at once, all under this key, each with its own
+        nonce (a device uint8 [n, 7 .. 13] tensor: its width is the batch's
+        nonce length) and AAD: ``(outs, tags)`` with ``tag_bytes``-long tags
+        (``ops.ccm_batch_ops.CcmBatch``)."""
+        return ops.ccm_batch_ops.ccm_encrypt_batch(xs, self._key, nonces, aads=aads, outs=outs, tag_bytes=tag_bytes)
+
+    def ccm_decrypt_batch(self, xs, nonces, tags, aads=None, outs=None):
+        """``(outs, ok)``: ``ok`` is a device bool [n] tensor, and the output
+        of every record whose tag (a device uint8 [n, tag length] tensor) does
+        not match is zeroed."""
+        return ops.ccm_batch_ops.ccm_decrypt_batch(xs, self._key, nonces, tags, aads=aads, outs=outs)
+
     # ---- authenticated: batched AES-GCM-SIV (RFC 8452), nonce-misuse resistant ----
     def gcm_siv_encrypt_batch(self, xs, nonces, aads=None, outs=None):
         """Many GPU records at once, this key (16 or 32 bytes) as the

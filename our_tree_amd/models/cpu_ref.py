@@ -487,6 +487,77 @@ def ocb_batch(key: bytes, nonces, datas, aads=None, decrypt: bool = False):
     return [ocb(key, n, d, a, decrypt=decrypt) for n, d, a in zip(nonces, datas, aads)]
 
 
+CCM_NONCE_BYTES = tuple(range(7, 14))  # L = 15 - len(nonce): 8 .. 2 bytes of length field
+CCM_TAG_BYTES = (4, 6, 8, 10, 12, 14, 16)
+
+
+class CcmTagError(ValueError):
+    """The tag of an AES-CCM message did not match; the plaintext was zeroed."""
+
+
+def ccm_check(nonce_bytes: int, tag_bytes: int, nbytes: int = 0):
+    """What every CCM call checks of its nonce length (7..13 bytes), its tag
+    length (4, 6, .., 16 bytes) and its message length (below 2**(8 L) with
+    L = 15 - nonce length): ValueError, as the device ops raise."""
+    if not isinstance(nonce_bytes, int) or nonce_bytes not in CCM_NONCE_BYTES:
+        raise ValueError("a CCM nonce has 7 to 13 bytes")
+    if not isinstance(tag_bytes, int) or tag_bytes not in CCM_TAG_BYTES:
+        raise ValueError("a CCM tag has 4, 6, 8, 10, 12, 14 or 16 bytes")
+    if nbytes >> (8 * (15 - nonce_bytes)):
+        raise ValueError(f"a CCM message under a {nonce_bytes}-byte nonce has fewer than "
+                         f"2**{8 * (15 - nonce_bytes)} bytes")
+
+
+def ccm(key: bytes, nonce: bytes, data: bytes, aad: bytes = b"", decrypt: bool = False, tag_bytes: int = 16):
+    """AES-CCM (SP 800-38C, RFC 3610) of one message: ``(out, tag)`` with the
+    COMPUTED ``tag_bytes``-long tag in both directions."""
+    ctx = _ctx(key)
+    nonce, data, aad = bytes(nonce), bytes(data), bytes(aad)
+    ccm_check(len(nonce), tag_bytes, len(data))
+    out, tag = _buf(len(data)), _buf(16)
+    rc = _native.cpu_lib().aes_crypt_ccm(ctypes.byref(ctx), AES_DECRYPT if decrypt else AES_ENCRYPT, len(data),
+                                         _native.as_u8p(nonce), len(nonce), _native.as_u8p(aad), len(aad),
+                                         _native.as_u8p(data), out, tag, tag_bytes)
+    if rc:
+        raise ValueError("invalid CCM lengths")
+    return bytes(out)[: len(data)], bytes(tag)[:tag_bytes]
+
+
+def ccm_auth_decrypt(key: bytes, nonce: bytes, data: bytes, tag: bytes, aad: bytes = b"") -> bytes:
+    """Authenticated decryption: the tag length is ``len(tag)``; compares in
+    constant time and raises CcmTagError (the C side zeroes its output) on a
+    mismatch."""
+    ctx = _ctx(key)
+    nonce, data, aad, tag = bytes(nonce), bytes(data), bytes(aad), bytes(tag)
+    ccm_check(len(nonce), len(tag), len(data))
+    # not zero to begin with: err.output shows what the C side left on a mismatch
+    out = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(b"\xa5" * max(len(data), 1))
+    rc = _native.cpu_lib().aes_ccm_auth_decrypt(ctypes.byref(ctx), len(data), _native.as_u8p(nonce), len(nonce),
+                                                _native.as_u8p(aad), len(aad), _native.as_u8p(tag), len(tag),
+                                                _native.as_u8p(data), out)
+    if rc == -0x16:
+        err = CcmTagError("CCM tag mismatch")
+        err.output = bytes(out)[: len(data)]
+        raise err
+    if rc:
+        raise ValueError("invalid CCM lengths")
+    return bytes(out)[: len(data)]
+
+
+def ccm_batch(key: bytes, nonces, datas, aads=None, decrypt: bool = False, tag_bytes: int = 16):
+    """The batched AES-CCM oracle: a loop over ``ccm``.  Record ``m`` is CCM
+    under ``(key, nonces[m], aads[m])``; one nonce length and one tag length
+    for the batch: a list of ``(out, tag)`` with the COMPUTED tags in both
+    directions."""
+    nonces, datas = [bytes(n) for n in nonces], [bytes(d) for d in datas]
+    aads = [b""] * len(datas) if aads is None else [bytes(a) for a in aads]
+    if len(nonces) != len(datas) or len(aads) != len(datas):
+        raise ValueError("one nonce and one AAD per record")
+    if len({len(n) for n in nonces}) > 1:
+        raise ValueError("a CCM batch has one nonce length")
+    return [ccm(key, n, d, a, decrypt=decrypt, tag_bytes=tag_bytes) for n, d, a in zip(nonces, datas, aads)]
+
+
 CHACHA_MAX_BYTES = ((1 << 32) - 1) * 64  # chacha.h CHACHA20_POLY1305_MAX_BYTES
 
 

@@ -10,6 +10,7 @@ from .chacha_ops import (ChaChaTagError, chacha20, chacha20_poly1305_decrypt, ch
 from . import chacha_batch_ops  # batched ChaCha20-Poly1305: its names are not in __all__ yet (docs/API.md)
 from . import ocb_ops  # AES-OCB3: its names are not in __all__ yet either (docs/API.md)
 from . import ocb_batch_ops  # batched AES-OCB3: the same arrangement (docs/API.md)
+from . import ccm_batch_ops  # batched AES-CCM and its single-message calls: the same arrangement (docs/API.md)
 from . import gcm_siv_ops  # AES-GCM-SIV and POLYVAL: the same arrangement (docs/API.md)
 from . import gcm_siv_batch_ops  # batched AES-GCM-SIV: the same arrangement (docs/API.md)
 from . import gcm_mk_batch_ops  # batched AES-GCM with a key per record: the same arrangement (docs/API.md)
